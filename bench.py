@@ -11,19 +11,27 @@ connections per GPU into that gateway.  Payloads are ResNet-shaped (3x224x224 fl
 ~1.1 MB of JSON) and unique per request, so every request is a real inference (no cache hits).
 Weights are random-init (no checkpoint offline).
 
-After the headline (and only reported as extra keys): the same requests straight to the worker
-(`direct_worker`), and BASELINE config 4 -- ONE data-parallel worker over all N ranks with RCCL
+A plain run sets up, warms up, times the K steps and prints the result line.  With --full, and only
+reported as extra keys: every 50th timed request carries a fixed input whose answer is checked
+against the CPU executor (`verify`; a mismatch zeroes the value), and after the headline the same
+requests go straight to the worker (`direct_worker`), through a gateway that re-sends the bodies
+(`gateway_bytes`), through the reference's own client and topology (`ref_client`), and through
+BASELINE config 4 -- ONE data-parallel worker over all N ranks with RCCL
 (weights ncclBroadcast from rank 0, per-batch logits + decode status ncclAllGather over xGMI; at
 N=1 the multi-rank merge path is forced so the communicator still forms) -- run in child processes
 under a watchdog, as `dp_rccl` ({"error": ...} if it fails or hangs; the headline is never lost).
+
+--dump-outputs DIR writes what the last timed step computed, as a client received it: the logits of
+that step's requests in request order, [step-requests, classes] float32, as DIR/logits.npy (rank r
+of N > 1: DIR/logits_rank<r>.npy; a failed request's row is NaN).  Those requests' inputs depend on
+the arguments and the request number alone, so two builds can be compared output for output.
 
 A "step" = --step-requests (500) requests per GPU, so the driver's `--steps 20` times 10,000
 requests per GPU: the reference's run length.  W warmup steps (after engine autotune and graph
 capture), then exactly K timed steps bracketed by barrier + torch.cuda.synchronize() (the client's
 payload templates are built before the opening barrier: loadgen's on_ready hook); the max wall
 time over ranks is the job time and `value` = total successful requests / that time (whole job,
-all GPUs).  The same count of requests sent straight to the worker (no gateway hop) is reported as
-the extra key `direct_worker`.
+all GPUs).
 """
 import argparse
 import json
@@ -67,6 +75,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--step-requests", type=int, default=500,
                     help="requests per GPU per step (20 steps = the reference's 10k requests)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: sampled answer verification against the CPU "
+                         "executor, direct_worker, gateway_bytes, dp_rccl and ref_client (each has its own --no-... "
+                         "switch); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the logits of the last timed step's requests (request order) as DIR/logits.npy")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--connections", type=int, default=50, help="client connections per GPU (reference: 50 threads)")
     ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32",
@@ -172,7 +186,7 @@ def main():
     ap.add_argument("--dp-steps", type=int, default=0, help="timed steps of the dp_rccl measurement (0 = --steps)")
     ap.add_argument("--dp-timeout", type=float, default=240.0, help="watchdog of the dp_rccl measurement (s)")
     ap.add_argument("--verify-every", type=int, default=50,
-                    help="every Nth timed request carries one of 8 fixed inputs whose logits the CPU executor "
+                    help="--full: every Nth timed request carries one of 8 fixed inputs whose logits the CPU executor "
                          "computed beforehand; its answer is checked (0 = off; a mismatch zeroes the value)")
     ap.add_argument("--no-ring-balance", action="store_true",
                     help="N>1 gateway mode: ephemeral worker ports instead of ring-balanced ones")
@@ -235,6 +249,15 @@ def main():
         r_ = native.loadgen(on_ready=ready, **kw)
         barrier()
         return r_, time.perf_counter() - t["t0"], t["ru0"]
+
+    def dump_outputs(y):
+        """--dump-outputs: the last timed step's answers, as the caller of the timed path got them."""
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "logits.npy" if world == 1 else "logits_rank%d.npy" % rank
+        np.save(os.path.join(args.dump_outputs, name), np.ascontiguousarray(y, np.float32))
+
     if args.arch == "vit_b16":
         from die_amd.models import vit as r
 
@@ -272,11 +295,16 @@ def main():
     extra = {}
 
     SR = args.step_requests
+    capture = {}
+    if args.dump_outputs:
+        # the last step's requests (fewer if all ranks' answers together would pass 64 MB)
+        rows = max(1, min(SR, (64 << 20) // (4 * cfg.num_classes * world)))
+        capture = dict(capture_from=max(0, args.steps * SR - rows), capture_numel=cfg.num_classes)
     # Answer verification: K fixed inputs, logits from the CPU executor (fp32, an
     # independent implementation of the same ONNX graph); the timed pass sends every Nth request as
     # one of them, with its text zero-padded per request so it is computed, never a cache hit.
     verify = None
-    if args.verify_every > 0 and args.mode in ("gateway", "http"):
+    if args.full and args.verify_every > 0 and args.mode in ("gateway", "http"):
         import numpy as np
 
         v4 = r.synthetic_input(8, cfg, seed=4242).astype(np.float32)
@@ -362,8 +390,11 @@ def main():
                                       e.get("avg_device_ms", 0.0)))
                 threading.Thread(target=_sampler, daemon=True).start()
         res, elapsed, ru0 = timed_loadgen(start=_start, port=target_port, requests=args.steps * SR, warmup=0,
-                                          id_prefix="r%d_" % rank, seed=2000 + rank, **dict(lg, **(verify or {})))
+                                          id_prefix="r%d_" % rank, seed=2000 + rank,
+                                          **dict(lg, **(verify or {}), **capture))
         stop_trace.set()
+        if capture:
+            dump_outputs(res.pop("captured_outputs"))
         t0 = tt["t0"]
         ru1 = resource.getrusage(resource.RUSAGE_SELF)
         h1 = wk.health()
@@ -451,7 +482,7 @@ def main():
                                      # the same routing on the reference's own layout (ports
                                      # 8001.., sequential "req_<i>" ids), next to the tuned deployment
                                      reference_layout=rb.reference_layout(world, args.steps * SR * world))
-        if gw and not args.no_direct:
+        if gw and args.full and not args.no_direct:
             # informative: the same request count straight to this rank's worker (no gateway hop)
             barrier()
             hd0 = wk.health()
@@ -473,9 +504,9 @@ def main():
                                       "p99_by_tenth_ms": [round(v, 2) for v in rd.get("p99_by_tenth_ms", [])],
                                       "slowest_ms": rd.get("slowest_ms", []),
                                       "stages_window_us": _stage_window(hd0.get("stages_us", {}), hd1.get("stages_us", {}))}
-        if gw and not args.no_gateway_bytes:
+        if gw and args.full and not args.no_gateway_bytes:
             # the reference's gateway hop: every body re-sent to the worker over loopback HTTP
-            # (/root/reference/src/gateway.cpp:99-103) instead of a shared-memory descriptor
+            # (the reference's src/gateway.cpp:99-103) instead of a shared-memory descriptor
             gwb = native.GatewayServer(["127.0.0.1:%d" % p for p in ports], client_threads=args.gw_client_threads,
                                        local_shm=False, http_threads=args.gw_http_threads,
                                        read_timeout_ms=5000 if hip else 120000)
@@ -490,9 +521,9 @@ def main():
         if gw:
             gw.stop()
         wk.stop()
-        if not args.no_dp:
+        if args.full and not args.no_dp:
             extra["dp_rccl"] = _dp_child(args, hg, rank, world)
-        if hip and args.arch == "resnet50" and args.mode == "gateway" and not args.no_ref_client:
+        if args.full and hip and args.arch == "resnet50" and args.mode == "gateway" and not args.no_ref_client:
             extra["ref_client"] = _ref_client(hg, rank, dev)
     elif args.mode == "dp":
         # BASELINE config 4: ONE data-parallel worker over all ranks.  Every rank serves HTTP on the
@@ -519,7 +550,9 @@ def main():
         native.loadgen(requests=args.warmup * SR, warmup=0, id_prefix="warm%d_" % rank, seed=1000 + rank, **lg)
         h0 = wk.health()
         res, elapsed, _ = timed_loadgen(requests=args.steps * SR, warmup=0, id_prefix="r%d_" % rank, seed=2000 + rank,
-                                        **lg)
+                                        **dict(lg, **capture))
+        if capture:
+            dump_outputs(res.pop("captured_outputs"))
         ok, failed = res["ok"], res["failed"]
         h1 = wk.health()
         e1 = h1["engine"]
@@ -561,10 +594,13 @@ def main():
             eng.run(x)
         barrier()
         t0 = time.perf_counter()
+        y = None
         for _ in range(args.steps):
-            eng.run(x)
+            y = eng.run(x)
         barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and y is not None:
+            dump_outputs(y)
         ok, failed = args.steps * B, 0
         # device_ms_per_batch: the in-graph forward (hipGraph replay of bucket B, events around it)
         extra = {"engine": eng.refresh_info()["name"], "device_ms_per_batch": eng.info.get("avg_device_ms"),

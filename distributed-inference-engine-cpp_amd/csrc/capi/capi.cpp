@@ -689,8 +689,11 @@ char* die_loadgen_run_verify(const char* opts_json, const float* inputs, long k,
 
 // Either form above (inputs == nullptr: no verification), with `on_ready` called on this thread
 // right before the timed phase starts (LoadgenOptions::on_ready).
-char* die_loadgen_run_cb(const char* opts_json, const float* inputs, long k, const float* expected, long out_numel,
-                         void (*on_ready)(void*), char** err) {
+// capture_out != nullptr: the answers of the timed requests from id capture_from on, capture_numel
+// floats each, land in capture_out (LoadgenOptions::capture_out).
+char* die_loadgen_run_capture(const char* opts_json, const float* inputs, long k, const float* expected, long out_numel,
+                              void (*on_ready)(void*), long capture_from, float* capture_out, long capture_numel,
+                              char** err) {
   try {
     LoadgenOptions o = loadgen_opts(Json::parse(opts_json));
     if (inputs) {
@@ -701,11 +704,19 @@ char* die_loadgen_run_cb(const char* opts_json, const float* inputs, long k, con
       o.output_numel = static_cast<size_t>(out_numel);
     }
     o.on_ready = on_ready;
+    o.capture_from = capture_from;
+    o.capture_out = capture_out;
+    o.capture_numel = static_cast<size_t>(capture_numel);
     return dup(run_loadgen(o).dump());
   } catch (const std::exception& e) {
     set_err(err, e.what());
     return nullptr;
   }
+}
+
+char* die_loadgen_run_cb(const char* opts_json, const float* inputs, long k, const float* expected, long out_numel,
+                         void (*on_ready)(void*), char** err) {
+  return die_loadgen_run_capture(opts_json, inputs, k, expected, out_numel, on_ready, 0, nullptr, 0, err);
 }
 
 }  // extern "C"

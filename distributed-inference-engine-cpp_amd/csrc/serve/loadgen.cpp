@@ -180,6 +180,22 @@ double response_error(const std::string& body, const float* ref, size_t n, const
   return den > 0.0 ? std::sqrt(num / den) : std::sqrt(num);
 }
 
+// A response's output_data as floats into out[0..n); false (out untouched) unless it is n numbers.
+bool response_output(const std::string& body, float* out, size_t n) {
+  Json j;
+  try {
+    j = Json::parse(body);
+  } catch (const std::exception&) {
+    return false;
+  }
+  const Json* o = j.find("output_data");
+  if (!o || !o->is_array() || o->size() != n) return false;
+  for (size_t i = 0; i < n; ++i)
+    if (!(*o)[i].is_number()) return false;
+  for (size_t i = 0; i < n; ++i) out[i] = static_cast<float>((*o)[i].as_double());
+  return true;
+}
+
 void patch_digits(std::string& b, size_t pos, size_t width, uint64_t v) {
   for (size_t k = 0; k < width; ++k) {
     b[pos + width - 1 - k] = static_cast<char>('0' + v % 10);
@@ -232,6 +248,19 @@ Json run_loadgen(const LoadgenOptions& o) {
   };
   std::vector<long> verified(C, 0), mismatched(C, 0), bad_id(C, 0);
   std::vector<double> max_err(C, 0.0);
+  // captured answers (LoadgenOptions::capture_out): kept as text during the timed phase (each slot
+  // is written by the one connection that took the id) and parsed after it
+  const bool capture = o.capture_out && o.capture_numel > 0 && o.capture_from >= 0 && o.capture_from < o.requests;
+  auto is_capture = [&](long id) { return capture && id >= o.capture_from && id < o.requests; };
+  std::vector<std::string> captured(capture ? static_cast<size_t>(o.requests - o.capture_from) : 0);
+  const uint64_t capture_seed = o.seed * 7919 + 1000003;
+  std::atomic<long> n_captured{0};
+  // connection c's share of the parsing, once every client has passed the closing gate
+  auto parse_captured = [&](int c) {
+    for (size_t i = static_cast<size_t>(c); i < captured.size(); i += static_cast<size_t>(C))
+      if (!captured[i].empty() && response_output(captured[i], o.capture_out + i * o.capture_numel, o.capture_numel))
+        ++n_captured;
+  };
   const int d = std::max(1, std::min(o.decimals, 8));
   uint64_t scale = 1;
   for (int k = 0; k < d; ++k) scale *= 10;
@@ -240,8 +269,13 @@ Json run_loadgen(const LoadgenOptions& o) {
   // in place per request), or a verify / reference body.  A body stays untouched until its request
   // has been sent completely (one request in flight per connection).
   struct Bodies {
-    Template tpl;
+    Template tpl, cap;  // cap: the shared template of captured requests (capture only)
     std::string vbody, small;
+  };
+  auto make_bodies = [&](Bodies& bd, int c) {
+    if (!full) return;
+    bd.tpl = make_full_template(o, o.seed * 7919 + static_cast<uint64_t>(c));
+    if (capture) bd.cap = make_full_template(o, capture_seed);
   };
   auto body_for = [&](Bodies& bd, int c, long id) -> const std::string& {
     if (is_verify(id)) {
@@ -259,10 +293,11 @@ Json run_loadgen(const LoadgenOptions& o) {
     }
     const long key = o.distinct > 0 ? id % o.distinct : id;
     if (full) {
-      Template& tpl = bd.tpl;
+      const bool cap = is_capture(id);
+      Template& tpl = cap ? bd.cap : bd.tpl;
       patch_digits(tpl.body, tpl.id_pos, tpl.id_len, printed(id));
-      // unique input: encode (key, connection) in the first two values
-      const uint64_t u = static_cast<uint64_t>(key) * 64 + static_cast<uint64_t>(c);
+      // unique input: encode (key, connection) in the first two values (a captured request: key alone)
+      const uint64_t u = cap ? static_cast<uint64_t>(key) : static_cast<uint64_t>(key) * 64 + static_cast<uint64_t>(c);
       patch_digits(tpl.body, tpl.v0_pos + 2, static_cast<size_t>(d), u % scale);
       patch_digits(tpl.body, tpl.v1_pos + 2, static_cast<size_t>(d), (u / scale) % scale);
       return tpl.body;
@@ -280,6 +315,7 @@ Json run_loadgen(const LoadgenOptions& o) {
       ++ok[c];
       lat[c].push_back(ms);
       when[c].emplace_back(std::chrono::duration<double, std::milli>(s - t0).count(), ms);
+      if (is_capture(id)) captured[static_cast<size_t>(id - o.capture_from)] = body;
       if (is_verify(id)) {
         const size_t k = verify_k(id);
         char idbuf[32];
@@ -436,7 +472,7 @@ Json run_loadgen(const LoadgenOptions& o) {
     };
     for (size_t i = 0; i < cs.size(); ++i) {
       cs[i].c = mine[i];
-      if (full) cs[i].bd.tpl = make_full_template(o, o.seed * 7919 + static_cast<uint64_t>(mine[i]));
+      make_bodies(cs[i].bd, mine[i]);
       open_conn(cs[i]);
     }
     std::vector<char> rbuf(1 << 16);
@@ -478,7 +514,8 @@ Json run_loadgen(const LoadgenOptions& o) {
               k.busy = false;
               if (k.record)
                 finish(k.c, k.id, k.start, k.status,
-                       is_verify(k.id) ? k.in.substr(k.hdr_end + 4, k.clen) : std::string(), std::string());
+                       is_verify(k.id) || is_capture(k.id) ? k.in.substr(k.hdr_end + 4, k.clen) : std::string(),
+                       std::string());
               if (closed) open_conn(k);
               next_id(k);
             } else if (closed) {
@@ -499,6 +536,7 @@ Json run_loadgen(const LoadgenOptions& o) {
       }
     }
     gate.arrive();
+    for (int c : mine) parse_captured(c);
     for (auto& k : cs)
       if (k.fd >= 0) ::close(k.fd);
     ::close(ep);
@@ -524,7 +562,7 @@ Json run_loadgen(const LoadgenOptions& o) {
         pthread_setname_np(pthread_self(), "die-loadgen");
         HttpClient client(o.host, o.port, std::chrono::milliseconds(o.timeout_ms), std::chrono::milliseconds(o.timeout_ms), 2);
         Bodies bd;
-        if (full) bd.tpl = make_full_template(o, o.seed * 7919 + static_cast<uint64_t>(c));
+        make_bodies(bd, c);
         auto one = [&](long id, bool record) {
           const std::string& body = body_for(bd, c, id);
           auto s = std::chrono::steady_clock::now();
@@ -546,6 +584,7 @@ Json run_loadgen(const LoadgenOptions& o) {
           one(id, true);
         }
         gate.arrive();
+        parse_captured(c);
       });
     }
   }
@@ -618,6 +657,7 @@ Json run_loadgen(const LoadgenOptions& o) {
   j["errors"] = e;
   j["payload"] = o.payload;
   j["body_bytes"] = static_cast<long long>(verify ? vt[0].body.size() : full ? make_full_template(o, 1).body.size() : 60);
+  if (capture) j["captured"] = static_cast<long long>(n_captured.load());
   if (verify || sampled) {
     long nv = 0, nm = 0, nb = 0;
     double me = 0.0;

@@ -52,6 +52,15 @@ struct LoadgenOptions {
   // connection (same closed loop, one request in flight per connection), so the client takes less
   // of a CPU share it shares with the server under test.
   int io_threads = 0;
+  // Capture (capture_out != nullptr): the output_data of every timed request with id >= capture_from
+  // is written to capture_out[(id - capture_from) * capture_numel ...] after the timed phase (the
+  // caller pre-fills the rows; a failed or malformed answer leaves its row as it was).  So that the
+  // captured rows are the same from run to run, a captured "full" request's input depends on its id
+  // alone: one template shared by all connections (seeded by `seed`), not the template of whichever
+  // connection happens to take the id.
+  long capture_from = 0;
+  float* capture_out = nullptr;
+  size_t capture_numel = 0;
   // Called once, on the calling thread, after every connection is open, its payload template built
   // and the warm-up done, right before the timed phase starts (bench.py: the barrier that opens the
   // timed window runs here, so building payloads is never inside it).

@@ -625,7 +625,8 @@ class GatewayServer:
 
 
 def loadgen(verify_inputs: Optional[np.ndarray] = None, verify_expected: Optional[np.ndarray] = None,
-            on_ready: Optional[Callable[[], None]] = None, **opts) -> Dict[str, Any]:
+            on_ready: Optional[Callable[[], None]] = None, capture_from: Optional[int] = None,
+            capture_numel: int = 0, **opts) -> Dict[str, Any]:
     """Closed-loop C++ load generator.  With verify_inputs ([K, input_numel]) and verify_expected
     ([K, output_numel]) every request carries one of the K inputs (unique request_id) and every answer
     is checked against its expected row (relative L2 <= verify_tol, 0 = bit-exact): the result adds
@@ -634,11 +635,15 @@ def loadgen(verify_inputs: Optional[np.ndarray] = None, verify_expected: Optiona
     hit); scramble_ids=True prints request numbers scrambled (hash-uniform on the gateway ring);
     io_threads=N > 0 drives the connections from N epoll threads instead of one thread each.
     on_ready() runs once, on this thread, after every connection's payloads are built and the warm-up
-    is done, right before the timed phase (the place for a timing barrier)."""
+    is done, right before the timed phase (the place for a timing barrier).
+    capture_from=I with capture_numel=N adds "captured_outputs": the output_data ([requests - I, N]
+    float32, NaN rows for failed requests) of the timed requests I.. in request order; those requests'
+    inputs depend on the seed and the request number alone (LoadgenOptions::capture_out)."""
     err = _err_box()
-    if on_ready is not None:
+    if on_ready is not None or capture_from is not None:
         def _cb(_arg):
-            on_ready()
+            if on_ready is not None:
+                on_ready()
         cb = _READY_CB(_cb)  # kept alive for the duration of the call
         xi = xe = None
         k = n_out = 0
@@ -647,6 +652,19 @@ def loadgen(verify_inputs: Optional[np.ndarray] = None, verify_expected: Optiona
             xe = np.ascontiguousarray(verify_expected, np.float32).reshape(len(xi), -1)
             opts = dict(opts, input_numel=xi.shape[1])
             k, n_out = len(xi), xe.shape[1]
+        if capture_from is not None:
+            rows = max(0, int(opts["requests"]) - int(capture_from))
+            cap = np.full((rows, int(capture_numel)), np.nan, np.float32)
+            fn = lib().die_loadgen_run_capture
+            fn.restype = C.c_void_p
+            fn.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_long, C.POINTER(C.c_float), C.c_long, _READY_CB,
+                           C.c_long, C.POINTER(C.c_float), C.c_long, C.POINTER(C.c_void_p)]
+            p = fn(json.dumps(opts).encode(), _f32(xi) if xi is not None else None, k,
+                   _f32(xe) if xe is not None else None, n_out, cb, int(capture_from), _f32(cap),
+                   int(capture_numel), C.byref(err))
+            if not p:
+                _raise_if(err, "loadgen")
+            return dict(json.loads(_take_str(p)), captured_outputs=cap)
         p = lib().die_loadgen_run_cb(json.dumps(opts).encode(), _f32(xi) if xi is not None else None, k,
                                      _f32(xe) if xe is not None else None, n_out, cb, C.byref(err))
         if not p:

@@ -49,8 +49,33 @@ def _check(out, n, steps, warmup, mode):
 
 
 STEP_REQ = 4
-ARGS = ["--device", "cpu", "--batch", "2", "--steps", "2", "--warmup", "1", "--connections", "4",
-        "--step-requests", str(STEP_REQ)]
+PLAIN = ["--device", "cpu", "--batch", "2", "--steps", "2", "--warmup", "1", "--connections", "4",
+         "--step-requests", str(STEP_REQ)]
+ARGS = PLAIN + ["--full"]  # everything beside the headline too (direct_worker, dp_rccl, verify, ...)
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """Without --full the run times the headline and nothing else; --dump-outputs writes the last
+    timed step's logits in request order, and a second run with the same arguments sends the same
+    inputs: the rows agree to float32 rounding (batch composition may differ between runs)."""
+    import numpy as np
+
+    outs = []
+    for d in ("a", "b"):
+        out = _run([sys.executable, "bench.py", "--mode", "gateway", "--arch", "resnet_tiny",
+                    "--dump-outputs", str(tmp_path / d)] + PLAIN)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in out, k
+        assert out["steps"] == 2 and out["config"]["requests"] == 2 * STEP_REQ and out["failed"] == 0
+        assert out["ms_per_step"] > 0 and abs(out["value"] * out["ms_per_step"] / 1e3 - STEP_REQ) < 1e-6 * STEP_REQ
+        for k in ("verify", "direct_worker", "gateway_bytes", "dp_rccl", "ref_client"):
+            assert k not in out, k
+        assert sorted(os.listdir(tmp_path / d)) == ["logits.npy"]
+        y = np.load(tmp_path / d / "logits.npy")
+        assert y.dtype == np.float32 and y.shape == (STEP_REQ, 10) and np.isfinite(y).all()
+        outs.append(y)
+    assert len({r.tobytes() for r in outs[0]}) == STEP_REQ  # distinct inputs, distinct answers
+    np.testing.assert_allclose(outs[0], outs[1], rtol=1e-5, atol=1e-6)
 
 
 @pytest.mark.parametrize("mode", ["gateway", "http", "dp"])
@@ -81,7 +106,8 @@ def test_bench_eight_ranks_torchrun_cpu(mode):
     out = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
                 "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "8",
                 "--mode", mode, "--arch", "resnet_tiny", "--device", "cpu", "--batch", "4", "--steps", "2",
-                "--warmup", "1", "--connections", "4", "--step-requests", "25", "--no-dp", "--verify-every", "10"],
+                "--warmup", "1", "--connections", "4", "--step-requests", "25", "--full", "--no-dp",
+                "--verify-every", "10"],
                timeout=600)
     assert out["n_gpus"] == 8 and out["failed"] == 0 and out["value"] > 0
     assert out["config"]["requests"] == 2 * 25 * 8

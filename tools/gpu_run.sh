@@ -38,7 +38,7 @@ EOF
 
 bench() {
   local n=$1; shift
-  timeout -k 10 600 python3 bench.py "$@" > "$O/$n.json" 2> "$O/$n.err" || { tail -20 "$O/$n.err"; return 1; }
+  timeout -k 10 600 python3 bench.py --full "$@" > "$O/$n.json" 2> "$O/$n.err" || { tail -20 "$O/$n.err"; return 1; }
   summ "$O/$n.json" "$n"
 }
 
@@ -83,7 +83,7 @@ case "$TASK" in
   rocprof)
     n=$1; shift
     cd /tmp && export TMPDIR=/tmp && cd "$R" || exit 1
-    timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/$n" -o p -- python3 bench.py --no-dp "$@" > "$O/$n.json" 2> "$O/$n.err" \
+    timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/$n" -o p -- python3 bench.py --full --no-dp "$@" > "$O/$n.json" 2> "$O/$n.err" \
       || { tail -20 "$O/$n.err"; exit 1; }
     summ "$O/$n.json" "$n"
     # rocprofv3 (ROCm 7.2) writes a rocpd SQLite database by default, CSVs with --output-format csv
