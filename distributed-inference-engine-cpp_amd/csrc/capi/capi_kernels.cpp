@@ -1,6 +1,7 @@
 // C ABI for launching individual HIP kernels on caller-provided device pointers (numerics tests
 // compare them with torch on the GPU box).  Pointers/streams travel as uint64 (torch data_ptr()
 // and torch.cuda.current_stream().cuda_stream).
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -195,6 +196,15 @@ int die_kern_attention(uint64_t q, uint64_t k, uint64_t v, uint64_t out, int B, 
                                           P<uint16_t>(out), B, Sq, H, D, ldq, ldk, ldv, ldo, scale, S(stream), split));
 }
 
+// bias: fp32 [bias_heads][Sq][Sp] pre-multiplied by log2(e) (kernels.h attention), 0 = none
+int die_kern_attention_masked(uint64_t q, uint64_t k, uint64_t v, uint64_t out, int B, int Sq, int H, int D, int ldq,
+                              int ldk, int ldv, int ldo, float scale, uint64_t stream, int split, uint64_t bias,
+                              int bias_heads, int Sp, int causal) {
+  return static_cast<int>(kern::attention(P<const uint16_t>(q), P<const uint16_t>(k), P<const uint16_t>(v),
+                                          P<uint16_t>(out), B, Sq, H, D, ldq, ldk, ldv, ldo, scale, S(stream), split,
+                                          P<const float>(bias), bias_heads, Sp, causal));
+}
+
 // geometry JSON: B,H,W,Cin,Ho,Wo,Cout,groups,KH,KW,stride,pad_h,pad_w,dil,act,clip_lo,clip_hi,split
 int die_kern_gconv(const char* geom, uint64_t x, uint64_t w, uint64_t bias, uint64_t out, uint64_t stream) {
   try {
@@ -367,6 +377,24 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
         e["rows"] = o.conv.Ho * o.conv.Wo;
         e["layernorm_folded"] = o.colsum_off != SIZE_MAX;
         e["stats_from_producer"] = o.in3_parts != 0;  // reads (merges) LayerNorm statistics partials
+      }
+      if (o.kind == PlanOp::ATTENTION) {
+        e["bias_heads"] = o.bias_heads;  // 0: no table, 1: one slice shared by the heads, nh: per head
+        e["causal"] = o.causal != 0;
+        if (o.bias_heads) {  // the folded table, back in natural units: sum of its finite entries, count of -inf
+          const int Sp = (o.S + 31) / 32 * 32;
+          const float* t = reinterpret_cast<const float*>(p.params.data() + o.bias_off);
+          double sum = 0;
+          long long masked = 0;
+          for (long long row = 0; row < static_cast<long long>(o.bias_heads) * o.S; ++row)
+            for (int c = 0; c < o.S; ++c) {
+              const float v = t[row * Sp + c];
+              if (std::isfinite(v)) sum += v;
+              else ++masked;
+            }
+          e["bias_sum"] = sum / 1.4426950408889634;
+          e["bias_masked"] = masked;
+        }
       }
       if (o.kind == PlanOp::LAYERNORM) e["stats_only"] = o.stats_only != 0;
       if (o.kind == PlanOp::CONV || o.kind == PlanOp::TOKENS) e["stats_out"] = o.out_stats >= 0;  // writes the partials

@@ -1460,7 +1460,9 @@ class HipEngine : public Engine {
           e = kern::attention(static_cast<const uint16_t*>(buf(op.in)) + op.col[0],
                               static_cast<const uint16_t*>(buf(op.in2)) + op.col[1],
                               static_cast<const uint16_t*>(buf(op.in3)) + op.col[2], static_cast<uint16_t*>(buf(op.out)),
-                              B, op.S, op.nh, op.hd, op.ld[0], op.ld[1], op.ld[2], op.C, op.fscale, st, sp_);
+                              B, op.S, op.nh, op.hd, op.ld[0], op.ld[1], op.ld[2], op.C, op.fscale, st, sp_,
+                              op.bias_heads ? prm(op.bias_off) : nullptr, op.bias_heads,
+                              op.bias_heads ? (op.S + 31) / 32 * 32 : 0, op.causal);
           break;
         case PlanOp::GCONV: {
           kern::GConvArgs g;
@@ -1562,6 +1564,10 @@ class HipEngine : public Engine {
         o["tile_order"] = t.order;
         o["tail_splitk"] = t.tail > 0;
         o["streamk_blocks"] = t.sk;
+      }
+      if (op.kind == PlanOp::ATTENTION) {
+        o["bias_heads"] = op.bias_heads;
+        o["causal"] = op.causal != 0;
       }
       total += us[i];
       ops.push_back(o);

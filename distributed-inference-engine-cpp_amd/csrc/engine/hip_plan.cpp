@@ -72,6 +72,7 @@ struct Val {
   std::array<int, 4> perm{{0, 1, 2, 3}};
   int q = -1, k = -1, v = -1, stage = 0;
   float scale = 1.f;
+  int mask = -1;  // ATTN stage 0/1/2: index of the folded bias / mask table (Planner::masks_), -1 = none
   // SHAPE / BCAST_INIT / TOKCAT
   std::vector<int64_t> ints;
   bool known = true;
@@ -115,7 +116,9 @@ class Planner {
         auto it = vid_.find(in);
         if (it != vid_.end() && vals_[it->second].kind == Val::UNKNOWN) blocked = true;
       }
-      if (blocked) {
+      // an Add / Where on attention scores whose mask came from an unsupported node is still tried:
+      // its own report line says that the mask must be an initializer
+      if (blocked && !attn_mask_node(n)) {
         report_.blocked++;
         mark_unknown(n);
         continue;
@@ -919,6 +922,109 @@ class Planner {
     return true;
   }
 
+  // ---- attention bias / mask folding --------------------------------------------------------------
+  // Between Q K^T and the Softmax a chain may hold, besides the scalar Div / Mul, any number of
+  // Add(scores, B) and Where(C, scores, f) nodes with B / C initializers broadcastable to
+  // [1, nh, S, S].  They fold at plan time into one dense additive table per attention, in the
+  // softmax's natural units: scores' = scale * (Q K^T) + table.  A later scale multiplies the table
+  // too, several Adds sum, a Where puts -inf at its masked positions.  emit_attention classifies
+  // the table (causal flag, shared / per-head, nothing left) and stores it.
+  struct AttnTable {
+    int heads = 1;         // 1 (shared) or nh
+    std::vector<float> t;  // [heads][S][S]
+  };
+  std::vector<AttnTable> masks_;  // indexed by Val::mask (a Val is copied by value everywhere)
+
+  // Add / Where with an attention-scores operand (stage 0)
+  bool attn_mask_node(const Node& n) const {
+    if (n.op_type != "Add" && n.op_type != "Where") return false;
+    for (const auto& in : n.inputs) {
+      auto it = vid_.find(in);
+      if (it != vid_.end() && vals_[it->second].kind == Val::ATTN && vals_[it->second].stage == 0) return true;
+    }
+    return false;
+  }
+
+  // The table of scores value x with room for `heads` slices (zeros when x has none yet).
+  AttnTable attn_table(const Val& x, int heads) const {
+    const size_t SS = static_cast<size_t>(vals_[x.q].H) * vals_[x.q].H;
+    AttnTable t;
+    if (x.mask >= 0) t = masks_[x.mask];
+    else t.t.assign(SS, 0.f);
+    if (t.heads < heads) {
+      t.t.resize(SS * heads);
+      for (int h = 1; h < heads; ++h) std::copy(t.t.begin(), t.t.begin() + SS, t.t.begin() + h * SS);
+      t.heads = heads;
+    }
+    return t;
+  }
+
+  // Checks a folded table and defines `out` = x with it.  +inf / NaN entries (a -inf entry scaled
+  // by a non-positive constant, inf - inf) have no meaning as a mask; a query row without any
+  // finite entry has an all-zero softmax denominator (NaN in ONNX, undefined on the device).
+  void define_masked(const Node& n, const Val& x, AttnTable t) {
+    const int S = vals_[x.q].H;
+    for (int h = 0; h < t.heads; ++h)
+      for (int i = 0; i < S; ++i) {
+        const float* row = t.t.data() + (static_cast<size_t>(h) * S + i) * S;
+        bool visible = false;
+        for (int j = 0; j < S; ++j) {
+          if (std::isnan(row[j]) || row[j] == INFINITY)
+            throw std::runtime_error(n.op_type + " " + n.name + ": the folded attention bias has a NaN / +inf entry (a mask "
+                                     "scaled by a constant that is not positive?)");
+          visible = visible || std::isfinite(row[j]);
+        }
+        if (!visible)
+          throw std::runtime_error(n.op_type + " " + n.name + ": attention mask leaves query row " + std::to_string(i) +
+                                   (t.heads > 1 ? " of head " + std::to_string(h) : std::string()) +
+                                   " with no visible key (its softmax is NaN in ONNX; the device kernel does not define it)");
+      }
+    Val o = x;
+    o.mask = static_cast<int>(masks_.size());
+    masks_.push_back(std::move(t));
+    define(n.outputs[0], o);
+  }
+
+  // Add(scores, B) / Where(C, scores, f) / Where(C, f, scores) on attention scores x.
+  // mode 0: add the float tensor; 1: -inf where the bool tensor is false; 2: -inf where it is true.
+  void lower_attn_mask(const Node& n, const Val& x, const std::string& tname, int mode) {
+    const char* what = mode == 0 ? "bias" : "mask";
+    auto it = m_.initializers.find(tname);
+    if (it == m_.initializers.end())
+      throw std::runtime_error(n.op_type + " " + n.name + ": the attention " + what + " " + tname +
+                               " must be an initializer (masks that depend on the input, and folding a mask the exporter "
+                               "left as a Slice / Cast / ... subgraph of constants, are out of scope)");
+    const onnx::Tensor& c = it->second;
+    const int S = vals_[x.q].H, nh = vals_[x.q].nh;
+    const size_t r = c.dims.size();
+    const bool typed = mode == 0 ? onnx::is_float_type(c.dtype) && static_cast<int64_t>(c.f.size()) == c.numel()
+                                 : c.dtype == onnx::BOOL && static_cast<int64_t>(c.i.size()) == c.numel();
+    if (!typed)
+      throw std::runtime_error(n.op_type + " " + n.name + ": the attention " + what + " " + tname + " must be a " +
+                               (mode == 0 ? "float" : "bool") + " tensor");
+    // right-aligned against [1, nh, S, S]: rank 2..4, leading dims 1 or nh, last two (S, S), (1, S) or (S, 1)
+    const int64_t dc = r >= 1 ? c.dims[r - 1] : 0, dr = r >= 2 ? c.dims[r - 2] : 0, dh = r >= 3 ? c.dims[r - 3] : 1,
+                  db = r >= 4 ? c.dims[0] : 1;
+    const bool rows_ok = (dr == S && dc == S) || (dr == 1 && dc == S) || (dr == S && dc == 1);
+    if (r < 2 || r > 4 || db != 1 || (dh != 1 && dh != nh) || !rows_ok) {
+      std::string shape;
+      for (auto d : c.dims) shape += (shape.empty() ? "" : ", ") + std::to_string(d);
+      throw std::runtime_error(n.op_type + " " + n.name + ": attention " + what + " " + tname + " [" + shape +
+                               "] does not broadcast to [1, " + std::to_string(nh) + ", " + std::to_string(S) + ", " +
+                               std::to_string(S) + "] (rank 2 to 4, leading dims 1 or the head count, last two dims (S, S), (1, S) or (S, 1))");
+    }
+    AttnTable t = attn_table(x, static_cast<int>(dh));
+    for (int h = 0; h < t.heads; ++h)
+      for (int i = 0; i < S; ++i)
+        for (int j = 0; j < S; ++j) {
+          const size_t src = ((dh == 1 ? 0 : static_cast<size_t>(h)) * dr + (dr == 1 ? 0 : i)) * dc + (dc == 1 ? 0 : j);
+          float& e = t.t[(static_cast<size_t>(h) * S + i) * S + j];
+          if (mode == 0) e += c.f[src];
+          else if ((c.i[src] != 0) == (mode == 2)) e = -INFINITY;
+        }
+    define_masked(n, x, std::move(t));
+  }
+
   // Materialise an attention context (logical [B, S, nh, hd]) as rows [B, S, nh*hd].
   int emit_attention(const Val& ctx, const std::string& name) {
     const Val& q = vals_[ctx.q];
@@ -928,6 +1034,9 @@ class Planner {
     if (!kern::attention_supported(q.hd, S) || k.H != S || v.H != S)
       throw std::runtime_error("attention " + name + ": needs head dim 32, 64, 80, 96 or 128 (64 and <= 256 tokens " +
                                "without the streaming kernel)");
+    if (ctx.mask >= 0 && !kern::attention_supported(q.hd, S, true))
+      throw std::runtime_error("attention " + name + ": a bias / mask on the scores needs the streaming attention kernel, "
+                               "which this build leaves out");
     PlanOp p;
     p.kind = PlanOp::ATTENTION;
     p.name = name;
@@ -946,6 +1055,41 @@ class Planner {
     p.fscale = ctx.scale;
     p.C = C;
     p.flops_per_sample = 4.0 * S * S * q.hd * q.nh;
+    if (ctx.mask >= 0) {
+      AttnTable t = masks_[ctx.mask];
+      const size_t SS = static_cast<size_t>(S) * S;
+      // a strict upper triangle of -inf in every head is the causal flag (the kernel masks from
+      // indices and skips the tiles); what remains of the table is its lower triangle
+      bool causal = S > 1;
+      for (int h = 0; h < t.heads && causal; ++h)
+        for (int i = 0; i < S && causal; ++i)
+          for (int j = i + 1; j < S; ++j)
+            if (t.t[h * SS + static_cast<size_t>(i) * S + j] != -INFINITY) {
+              causal = false;
+              break;
+            }
+      if (causal)
+        for (int h = 0; h < t.heads; ++h)
+          for (int i = 0; i < S; ++i)
+            for (int j = i + 1; j < S; ++j) t.t[h * SS + static_cast<size_t>(i) * S + j] = 0.f;
+      bool same = true;  // all heads equal: one shared slice
+      for (int h = 1; h < t.heads && same; ++h) same = std::equal(t.t.begin(), t.t.begin() + SS, t.t.begin() + h * SS);
+      if (same) {
+        t.heads = 1;
+        t.t.resize(SS);
+      }
+      const bool zero = std::all_of(t.t.begin(), t.t.end(), [](float e) { return e == 0.f; });
+      if (!zero) {  // [heads][S][Sp], rows padded to a multiple of 32, in the kernel's exp2 units
+        const int Sp = (S + 31) / 32 * 32;
+        std::vector<float> tab(static_cast<size_t>(t.heads) * S * Sp, 0.f);
+        for (size_t row = 0; row < static_cast<size_t>(t.heads) * S; ++row)
+          for (int j = 0; j < S; ++j) tab[row * Sp + j] = t.t[row * S + j] * 1.4426950408889634f;
+        p.bias_off = push_f32(tab);
+        p.bias_heads = t.heads;
+      }
+      p.causal = causal ? 1 : 0;
+      if (causal) p.flops_per_sample = 4.0 * q.hd * q.nh * (static_cast<double>(S) * (S + 1) / 2);
+    }
     p.out = new_buf(static_cast<size_t>(S) * C * 2);
     const int buf = p.out;
     add_op(std::move(p));
@@ -1172,6 +1316,11 @@ class Planner {
       if (x.kind == Val::ATTN && x.stage == 0 && it != m_.initializers.end() && it->second.f.size() == 1) {
         Val o = x;
         o.scale = n.op_type == "Div" ? x.scale / it->second.f[0] : x.scale * it->second.f[0];
+        if (x.mask >= 0) {  // a scale after an Add / Where reaches the accumulated bias as well
+          AttnTable t = masks_[x.mask];
+          for (float& e : t.t) e = n.op_type == "Div" ? e / it->second.f[0] : e * it->second.f[0];
+          return define_masked(n, o, std::move(t));
+        }
         define(n.outputs[0], o);
         return;
       }
@@ -1703,6 +1852,22 @@ class Planner {
   // Where(cond, a, b): cond an activation; a / b activations of cond's shape or scalar constants.
   void lower_where(int idx) {
     const Node& n = m_.nodes[idx];
+    // Where(C, scores, f) / Where(C, f, scores) on attention scores: a constant mask.  The fill f
+    // (<= -1e4: GPT-2's -1e4, -1e9, finfo.min, -inf) is treated as -inf -- for scores of ordinary
+    // size (|score - row max| far below 1e4) an fp32 softmax gives such positions exactly zero
+    // weight either way.  A finite fill above -1e4 is a value, not a mask.
+    for (int side = 1; side <= 2 && n.inputs.size() == 3; ++side) {
+      auto it = vid_.find(n.in(side));
+      if (it == vid_.end() || vals_[it->second].kind != Val::ATTN || vals_[it->second].stage != 0) continue;
+      const Val x = vals_[it->second];
+      float f = 0.f;
+      if (!scalar_init(n.in(3 - side), f))
+        throw std::runtime_error("Where " + n.name + ": on attention scores the other branch must be a scalar initializer");
+      if (!(f <= -1e4f))
+        throw std::runtime_error("Where " + n.name + ": fill " + std::to_string(f) + " is not a mask (only fills <= -1e4 or "
+                                 "-inf fold into the attention kernel as -inf); a finite fill above -1e4 is not supported");
+      return lower_attn_mask(n, x, n.in(0), side == 1 ? 1 : 2);
+    }
     const Val c = materialize_in(n.in(0), n);
     if (!dense(c)) throw std::runtime_error("Where " + n.name + ": the condition must be a dense activation");
     PlanOp p;
@@ -1955,6 +2120,14 @@ class Planner {
 
   void lower_add(int idx) {
     const Node& n = m_.nodes[idx];
+    // attention scores + constant bias / mask table -> folded into the attention op
+    for (int side = 0; side < 2 && n.inputs.size() == 2; ++side) {
+      auto it = vid_.find(n.in(side));
+      if (it != vid_.end() && vals_[it->second].kind == Val::ATTN && vals_[it->second].stage == 0) {
+        const Val x = vals_[it->second];
+        return lower_attn_mask(n, x, n.in(1 - side), 0);
+      }
+    }
     // [cls, patches] + position embedding -> token assembly
     for (int side = 0; side < 2; ++side) {
       auto it = vid_.find(n.in(side));

@@ -13,6 +13,17 @@
 //  * transformers (ViT): the patch Conv's Reshape/Transpose, the heads Reshape/Transpose, the
 //    MatMul -> Div -> Softmax -> MatMul chain and the shape-computation subgraph are all lazy views;
 //    the chain materialises as one fused attention kernel when the context is merged back into rows.
+//    Between Q K^T and the Softmax the chain also takes, in any number and order, Add(scores, B)
+//    with a float initializer B and Where(C, scores, f) / Where(C, f, scores) with a bool
+//    initializer C and a scalar fill f <= -1e4 (taken as -inf), B / C broadcastable to
+//    [1, nh, S, S] (rank 2 to 4, leading dims 1 or nh, last two (S, S), (1, S) or (S, 1)).  They
+//    fold into one additive table per attention (a later scale multiplies it, Adds sum), which is
+//    classified: a -inf strict upper triangle becomes the kernel's causal flag, equal heads one
+//    shared slice, an all-zero remainder no table at all (causal masks, relative-position / ALiBi
+//    tables, BERT key masks, sliding windows).  Rejected with a report line: shapes that do not
+//    broadcast, a finite fill above -1e4, a query row with no visible key, and a mask that is not an
+//    initializer -- masks that depend on the input (there is no second graph input), folding of
+//    mask-building Slice / Cast subgraphs, cross-attention and KV caches are out of scope.
 //    Sibling Q/K/V MatMuls become one GEMM (N = 3*D); MatMul -> Add(bias) -> erf-GELU and
 //    MatMul -> Add(bias) -> Add(residual) fold into the GEMM epilogue; cls Expand/Concat + position
 //    Add -> one token-assembly kernel; LayerNormalization and Gather(token) -> row kernels.
@@ -81,6 +92,10 @@ struct PlanOp {
   int S = 0, nh = 0, hd = 0, gidx = 0;
   int col[3] = {0, 0, 0}, ld[3] = {0, 0, 0};
   float fscale = 1.f, eps = 0.f;
+  // ATTENTION with a folded bias / mask: bias_off = fp32 table [bias_heads][S][S rounded up to 32] in
+  // the kernel's exp2 units (kern::attention), bias_heads = 0 (none), 1 (shared) or nh; causal = 1:
+  // key j visible to query i iff j <= i
+  int bias_heads = 0, causal = 0;
   double flops_per_sample = 0;
   // Side branch: this op may run on a second stream, concurrently with the ops after it, until
   // op `join` (its first consumer) waits for it.  The arena keeps its inputs live until `join`.

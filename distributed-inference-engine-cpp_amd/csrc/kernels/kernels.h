@@ -348,8 +348,9 @@ hipError_t decode_json_numbers(const unsigned char* text, const long long* offs,
 void set_attention_variant(int v);
 bool attention_any_length();
 // Head dim / sequence length the attention launcher takes (streaming kernel: head dim 32, 64, 80,
-// 96 or 128, any length; the whole-K/V kernel: 64 and <= 256 tokens).
-bool attention_supported(int D, int S);
+// 96 or 128, any length; the whole-K/V kernel: 64 and <= 256 tokens).  masked: with a bias and / or
+// the causal flag -- the streaming kernel only (a build without it has no masked attention).
+bool attention_supported(int D, int S, bool masked = false);
 // variant (measurement): 0 = the default choice, 1 = 16 lanes x 6 chunks per row (C <= 768: 4 rows
 // per wave, twice the loads in flight per lane), 2 = the block-per-row kernel.
 // LayerNorm row order (measurement switch, process-wide, read at launch): 1 = XCD-affine (rows read
@@ -371,8 +372,19 @@ hipError_t gather_rows(const uint16_t* x, uint16_t* y, int B, int S, int idx, in
 // Multi-head attention: out[b,s,h*D:(h+1)*D] = softmax(scale * Q_h K_h^T) V_h with Q/K/V rows
 // [B*S][ld*] (head h at columns h*D).  D and S as attention_supported() takes them (split: q/k/v/out
 // planes are B*S*ld of their pitch).
+// Masked: softmax(scale * Q K^T + bias) with
+//  * bias (nullable): fp32 in both precisions, [bias_heads][S][Sp] with bias_heads = 1 (shared by
+//    all heads) or H and Sp = S rounded up to a multiple of 32 (pad columns: any finite value),
+//    16-byte aligned, the same for every image of the batch.  Units: PRE-MULTIPLIED by log2(e) --
+//    the kernel's softmax runs in exp2 and adds the table to score * scale * log2(e) as it is;
+//    -inf = masked;
+//  * causal != 0: key j is visible to query i iff j <= i (from indices; combines with a bias).
+// A query row with no visible key at all is undefined (ONNX gives NaN): callers reject such masks.
+// Wrong bias_heads / Sp / alignment, or a mask on a build without the streaming kernel:
+// hipErrorInvalidValue, nothing launched.
 hipError_t attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, int B, int S, int H,
-                     int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t s, int split = 0);
+                     int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t s, int split = 0,
+                     const float* bias = nullptr, int bias_heads = 0, int Sp = 0, int causal = 0);
 
 }  // namespace kern
 }  // namespace die

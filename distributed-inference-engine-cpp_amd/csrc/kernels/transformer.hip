@@ -421,12 +421,34 @@ struct AttnGeom {
   static constexpr int LPT = (32 * CPR + 255) / 256;             // 16-B loads per thread per plane per tile
   static constexpr int NKS = HD / 16, NDT = (HD + 31) / 32;
   static constexpr int WAVES_PER_SIMD = HD > 96 && SPLIT ? 1 : (HD > 64 ? 2 : 3);
+  // Masked modes: the tile's 16 bias values (and the causal compares) are live across the K Q^T
+  // MFMAs; the split instantiations that would spill at the bound above get one wave less
+  // (resource figures: profiles/attention_masked.md).
+  static constexpr int waves_per_simd(bool bias, bool causal) {
+    if (!SPLIT || !(bias || causal)) return WAVES_PER_SIMD;
+    return HD == 64 ? 2 : HD == 80 || (HD == 96 && bias) ? 1 : WAVES_PER_SIMD;
+  }
 };
 
-template <bool SPLIT, bool DEEP, int HD>
-__global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::WAVES_PER_SIMD)) void attention_stream_kernel(
+//
+// Masked modes (compile-time; with both off the kernel is the unmasked one, its three trailing
+// arguments unused; K/V staged one tile ahead only -- DEEP stays an unmasked measurement variant):
+//  * BIAS: x = score * scale_log2 + bias[head][query][key], the bias an fp32 table [Hb][S][Sp]
+//    (Sp = S rounded up to 32, head stride bias_hs = 0 or S * Sp elements) in exp2 units (the host
+//    pre-multiplies by log2 e); -inf = masked.  A lane's 16 keys of a tile are four aligned 16-B
+//    loads of its query's row (rows >= S clamp to S - 1: their results are discarded), issued ahead
+//    of the tile's K Q^T MFMAs together with the next tile's K/V prefetch.
+//  * CAUSAL: key j visible to query i iff j <= i.  A block walks only the tiles up to its last
+//    query; a wave skips the math of tiles past its own queries (it still stages K/V and meets the
+//    barriers, like an idle wave); the diagonal tile masks per element.
+// A tile can be all -inf for a row while the row's running max is still -inf (a band mask from
+// query 32 on): the masked modes subtract 0 instead of that max, so p = alpha = 0 and o, l stay 0
+// until the row's first visible key.  A row with NO visible key is undefined (callers reject it).
+template <bool SPLIT, bool DEEP, int HD, bool BIAS = false, bool CAUSAL = false>
+__global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAUSAL))) void attention_stream_kernel(
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ v,
-    uint16_t* __restrict__ out, int S, int ldq, int ldk, int ldv, int ldo, float scale_log2, int xcd_map) {
+    uint16_t* __restrict__ out, int S, int ldq, int ldk, int ldv, int ldo, float scale_log2, int xcd_map,
+    const float* __restrict__ bias, long long bias_hs, int Sp) {
   using G = AttnGeom<HD, SPLIT>;
   constexpr int NP = SPLIT ? 2 : 1;
   constexpr int KT = 32;  // keys per tile
@@ -450,13 +472,18 @@ __global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::WAVES_PER_SIMD)) void at
       const int pair = xcd_map == 2 ? (lin & 7) * (pairs >> 3) + slot / nqb  // contiguous pair ranges
                                     : (lin & 7) + 8 * (slot / nqb);              // interleaved (default)
       qblk = slot % nqb;
+      // CAUSAL: a query block's work grows with its index, and blocks 32 slots apart (one round over
+      // an XCD's CUs) would hold the same index -- the last query blocks of three pairs on one CU,
+      // the first ones on another.  Rotate the index by the pair's round so a CU gets a mix.
+      if constexpr (CAUSAL) qblk = (qblk + 3 * ((slot / nqb) * nqb / 32)) % nqb;
       h = pair % gridDim.y;
       b = pair / gridDim.y;
     }
   }
   const long long rowbase = static_cast<long long>(b) * S;
   const long long rows = static_cast<long long>(gridDim.z) * S;  // plane distances: rows x pitch
-  const int nkt = (S + KT - 1) / KT;
+  // CAUSAL: the block's last query sees keys below min(S, 128 qblk + 128) only (block-uniform)
+  const int nkt = ((CAUSAL && qblk * 128 + 128 < S ? qblk * 128 + 128 : S) + KT - 1) / KT;
   // tile loader: load j of a thread = (key row, 16-B chunk) index tid + 256 j of every tensor plane
   typedef uint4 Stage[NP][LPT];
   Stage kr0, vr0, kr1, vr1;
@@ -517,15 +544,31 @@ __global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::WAVES_PER_SIMD)) void at
     for (int i = 0; i < 16; ++i) o[dt][i] = 0.f;
   float m = -INFINITY, l = 0.f;
   const int g = (lane >> 4) & 1, qq = (lane & 15) >> 2, pp = lane & 3;
+  // BIAS: this lane's query row of the table, at its lane half's first key of a tile
+  const float* brow = nullptr;
+  if constexpr (BIAS)
+    brow = bias + h * bias_hs + static_cast<long long>(q0 + r < S ? q0 + r : S - 1) * Sp + 4 * hh;
   // one key tile; (ka, va): the register set free for a new fetch, (kb, vb): tile kt+1 when DEEP
   auto step = [&](int kt, Stage& ka, Stage& va, Stage& kb, Stage& vb) {
     const int buf = kt & 1;
+    // CAUSAL: tiles past the wave's queries (first key > last query) are skipped, wave-uniform
+    const bool does = active && (!CAUSAL || kt * KT <= q0);
     if (DEEP) {
       if (kt + 2 < nkt) fetch(kt + 2, ka, va);  // in flight under this tile's and the next tile's MFMAs
     } else {
       if (kt + 1 < nkt) fetch(kt + 1, ka, va);  // in flight under this tile's MFMAs
     }
-    if (active) {
+    // BIAS: the tile's 16 values, issued with the K/V prefetch and ahead of the K Q^T MFMAs.  The
+    // compiler puts the step's one vmcnt wait in front of the first MFMA (in the unmasked kernel
+    // too); these loads share it and add no wait of their own.
+    float4 bv[4];
+    if constexpr (BIAS) {
+      if (does) {
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) bv[g4] = *reinterpret_cast<const float4*>(brow + kt * KT + 8 * g4);
+      }
+    }
+    if (does) {
       f32x16 sc;
 #pragma unroll
       for (int i = 0; i < 16; ++i) sc[i] = 0.f;
@@ -542,23 +585,35 @@ __global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::WAVES_PER_SIMD)) void at
         sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[0][ks], sc, 0, 0, 0);
       }
       float mt = -INFINITY;
-      if (kt * KT + KT <= S) {  // full tile (wave-uniform): no key mask
+      const bool diag = CAUSAL && kt * KT == q0;  // the wave's diagonal tile masks per element
+      if (kt * KT + KT <= S && !diag) {  // full tile (wave-uniform): no key mask
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          sc[i] *= scale_log2;
+          if constexpr (BIAS) sc[i] = fmaf(sc[i], scale_log2, bv[i >> 2][i & 3]);
+          else sc[i] *= scale_log2;
           mt = fmaxf(mt, sc[i]);
         }
       } else {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int key = kt * KT + (i & 3) + 8 * (i >> 2) + 4 * hh;
-          const float x = key < S ? sc[i] * scale_log2 : -INFINITY;
+          float x;
+          if constexpr (BIAS || CAUSAL) {
+            if constexpr (BIAS) x = fmaf(sc[i], scale_log2, bv[i >> 2][i & 3]);
+            else x = sc[i] * scale_log2;
+            if (!(key < S && (!diag || key <= q0 + r))) x = -INFINITY;
+          } else {
+            x = key < S ? sc[i] * scale_log2 : -INFINITY;
+          }
           sc[i] = x;
           mt = fmaxf(mt, x);
         }
       }
       mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-      const float mn = fmaxf(m, mt);
+      float mn = fmaxf(m, mt);
+      const float mkeep = mn;
+      // BIAS: every key so far masked (mn = -inf) -> subtract 0: alpha = p = 0, no inf - inf
+      if constexpr (BIAS) mn = mn == -INFINITY ? 0.f : mn;
       const float alpha = __builtin_amdgcn_exp2f(m - mn);  // m = -inf on the first tile: 0
       l *= alpha;
 #pragma unroll
@@ -571,7 +626,7 @@ __global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::WAVES_PER_SIMD)) void at
         sc[i] = p;
         l += p;
       }
-      m = mn;
+      m = mkeep;
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
         bf16x8 pf, pfl;
@@ -740,10 +795,10 @@ hipError_t softmax_rows(const uint16_t* x, uint16_t* y, float* y_f32, long long 
 
 bool attention_any_length() { return kAttnStream; }
 
-bool attention_supported(int D, int S) {
+bool attention_supported(int D, int S, bool masked) {
   if (S <= 0) return false;
   if (kAttnStream) return D == 32 || D == 64 || D == 80 || D == 96 || D == 128;
-  return D == AT_D && S <= 256;
+  return !masked && D == AT_D && S <= 256;  // the whole-K/V kernel has no masked modes
 }
 
 namespace {
@@ -752,17 +807,51 @@ int g_attn_variant = 0;  // 0: K/V staged one tile ahead, 1: two tiles ahead (DE
 void set_attention_variant(int v) { g_attn_variant = v; }
 
 hipError_t attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, int B, int S, int H,
-                     int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t s, int split) {
-  if (!attention_supported(D, S) || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4) return hipErrorInvalidValue;
+                     int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t s, int split,
+                     const float* bias, int bias_heads, int Sp, int causal) {
+  const bool masked = bias != nullptr || causal != 0;
+  if (!attention_supported(D, S, masked) || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4) return hipErrorInvalidValue;
+  if (bias) {  // [1 or H][S][Sp] fp32, rows of Sp = S rounded up to 32 (16-byte loads, in bounds in the last tile)
+    if ((bias_heads != 1 && bias_heads != H) || Sp != (S + 31) / 32 * 32 || reinterpret_cast<uintptr_t>(bias) % 16)
+      return hipErrorInvalidValue;
+  } else if (bias_heads != 0) {
+    return hipErrorInvalidValue;
+  }
   const float sl2 = scale * 1.4426950408889634f;  // softmax in exp2
   if (kAttnStream) {  // 4-wave blocks of 128 queries, K/V streamed in 32-key tiles (any S)
     dim3 grid((S + 127) / 128, H, B);
     const bool deep = g_attn_variant == 1;
     // variant 2: the natural block mapping, 3: contiguous pair ranges per XCD (measurement)
     const int xcd_map = g_attn_variant == 2 ? 0 : g_attn_variant == 3 ? 2 : 1;
+    if (masked) {  // one-tile-ahead staging only (the DEEP measurement variant stays unmasked)
+      const long long bias_hs = bias && bias_heads == H && H > 1 ? static_cast<long long>(S) * Sp : 0;
+#define ATTN_MASKED(SP, HDV, BI, CA)                                                                                 \
+  hipLaunchKernelGGL((attention_stream_kernel<SP, false, HDV, BI, CA>), grid, dim3(256), 0, s, q, k, v, out, S, ldq, ldk, \
+                     ldv, ldo, sl2, xcd_map, bias, bias_hs, Sp)
+#define ATTN_MASKED_HD(HDV)                                     \
+  if (split) {                                                  \
+    if (bias && causal) ATTN_MASKED(true, HDV, true, true);     \
+    else if (bias) ATTN_MASKED(true, HDV, true, false);         \
+    else ATTN_MASKED(true, HDV, false, true);                   \
+  } else {                                                      \
+    if (bias && causal) ATTN_MASKED(false, HDV, true, true);    \
+    else if (bias) ATTN_MASKED(false, HDV, true, false);        \
+    else ATTN_MASKED(false, HDV, false, true);                  \
+  }
+      switch (D) {
+        case 32: ATTN_MASKED_HD(32) break;
+        case 64: ATTN_MASKED_HD(64) break;
+        case 80: ATTN_MASKED_HD(80) break;
+        case 96: ATTN_MASKED_HD(96) break;
+        default: ATTN_MASKED_HD(128) break;
+      }
+#undef ATTN_MASKED_HD
+#undef ATTN_MASKED
+      return hipGetLastError();
+    }
 #define ATTN_LAUNCH(SP, DP, HDV)                                                                                   \
   hipLaunchKernelGGL((attention_stream_kernel<SP, DP, HDV>), grid, dim3(256), 0, s, q, k, v, out, S, ldq, ldk, ldv, ldo, \
-                     sl2, xcd_map)
+                     sl2, xcd_map, static_cast<const float*>(nullptr), 0LL, 0)
 #define ATTN_HD(HDV)                          \
   if (split && deep) ATTN_LAUNCH(true, true, HDV);    \
   else if (split) ATTN_LAUNCH(true, false, HDV);      \

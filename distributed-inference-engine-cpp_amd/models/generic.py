@@ -34,6 +34,11 @@ mix a ResNet / ViT never exercises, random weights, written by the in-tree ONNX 
 * `bert_long`  the `bert` encoder at 320 tokens: attention past 256 keys (streaming kernel).
 * `bert_hd32`, `bert_hd128`  the `bert` encoder with head dim 32 (4 heads of 128 features, 40 tokens)
               and 128 (2 heads of 256 features, 24 tokens).
+* `gpt_causal`  pre-LN decoder blocks with the GPT-2 causal mask, Where(tril, scores / sqrt(d), -1e4).
+* `bert_relpos` the `bert` encoder with a per-head relative-position table added to the scaled scores.
+* `bert_window` a shared band mask (0 inside |i - j| <= 8, -inf outside) added BEFORE the scale, 72
+              tokens: from row 41 on the first 32-key tile is entirely masked.
+* `bert_keymask` the BERT extended attention mask: Add of [1, 1, 1, S] with -10000 on the last 9 keys.
 `synthetic_input(model, batch)` gives inputs of the right shape.  The CPU executor is the fp32
 oracle for all of them (tests/test_gpu_general.py).
 """
@@ -59,7 +64,13 @@ SPECS = {
     "bert_long": dict(seq=320, dim=128, heads=2, ffn=256, layers=1, classes=3),
     "bert_hd32": dict(seq=40, dim=128, heads=4, ffn=256, layers=2, classes=3),
     "bert_hd128": dict(seq=24, dim=256, heads=2, ffn=512, layers=2, classes=3),
+    "gpt_causal": dict(seq=40, dim=128, heads=2, ffn=256, layers=2, classes=3),
+    "bert_relpos": dict(seq=40, dim=128, heads=4, ffn=256, layers=2, classes=3),
+    "bert_window": dict(seq=72, dim=128, heads=2, ffn=256, layers=2, classes=3, window=8),
+    "bert_keymask": dict(seq=40, dim=128, heads=2, ffn=256, layers=2, classes=3, masked_keys=9),
 }
+
+MASKED = ("gpt_causal", "bert_relpos", "bert_window", "bert_keymask")
 
 
 def _rng(seed):
@@ -155,6 +166,115 @@ def build_bert(seed: int = 0, opset: int = 17, spec: str = "bert") -> Tuple[byte
     y = g.node("Gemm", [pooled, w, b], name="classifier", transB=1)
     g.output(y, ["N", s["classes"]])
     return g.model_proto(opset=opset), {}
+
+
+def masked_score_ops(spec: str, seed: int = 0):
+    """The nodes between Q K^T and the Softmax of the masked-attention models: a function
+    (g, scores, prefix, layer) -> value.  All masks / tables are initializers."""
+    s = SPECS[spec]
+    S, H, hd = s["seq"], s["heads"], s["dim"] // s["heads"]
+    rng = _rng(seed + 1000)
+
+    def scale(g, v, p):
+        return g.node("Div", [v, g.const(np.array(math.sqrt(hd), np.float32), "sqrt_d")], name=p + "scale")
+
+    if spec == "gpt_causal":  # GPT-2 export: Where(tril, scores / sqrt(d), -1e4)
+        def ops(g, v, p, layer):
+            tril = g.init(p + "causal_mask", np.tril(np.ones((1, 1, S, S), np.bool_)))
+            fill = g.const(np.array(-1e4, np.float32), "mask_fill")
+            return g.node("Where", [tril, scale(g, v, p), fill], name=p + "causal")
+    elif spec == "bert_relpos":  # learned relative-position bias per head, after the scale
+        def ops(g, v, p, layer):
+            table = g.init(p + "rel_bias", rng.standard_normal((1, H, S, S)).astype(np.float32))
+            return g.node("Add", [scale(g, v, p), table], name=p + "rel_bias/Add")
+    elif spec == "bert_window":  # shared band mask added BEFORE the scale
+        def ops(g, v, p, layer):
+            i = np.arange(S)
+            band = np.where(np.abs(i[:, None] - i[None, :]) <= s["window"], 0.0, -np.inf).astype(np.float32)
+            return scale(g, g.node("Add", [v, g.init(p + "window_mask", band)], name=p + "window"), p)
+    elif spec == "bert_keymask":  # BERT extended attention mask: -10000 on the padded keys
+        def ops(g, v, p, layer):
+            m = np.zeros((1, 1, 1, S), np.float32)
+            m[..., S - s["masked_keys"]:] = -10000.0
+            return g.node("Add", [scale(g, v, p), g.init(p + "key_mask", m)], name=p + "key_mask/Add")
+    else:
+        raise KeyError(spec)
+    return ops
+
+
+def build_masked_encoder(seed: int = 0, opset: int = 17, spec: str = "bert_relpos", score_ops=None,
+                         pre_ln=None) -> Tuple[bytes, Dict[str, np.ndarray]]:
+    """Encoder / decoder stacks whose attention has a constant additive bias or mask between Q K^T and
+    the Softmax (`gpt_causal`, `bert_relpos`, `bert_window`, `bert_keymask`).  score_ops overrides
+    the nodes of that stretch (tests build further variants on the same stack); pre_ln: GPT-style
+    pre-LayerNorm blocks (default: for `gpt_causal`), else the `bert` post-LN blocks."""
+    s = SPECS[spec]
+    rng = _rng(seed)
+    S, D, H, F = s["seq"], s["dim"], s["heads"], s["ffn"]
+    hd = D // H
+    if score_ops is None:
+        score_ops = masked_score_ops(spec, seed)
+    if pre_ln is None:
+        pre_ln = spec == "gpt_causal"
+    g = GraphBuilder(name=spec)
+    x = g.input("embeddings", ["N", S * D])
+    h = g.node("Reshape", [x, g.const(np.array([0, S, D], np.int64), "seq_shape")], name="to_tokens")
+    heads_shape = g.const(np.array([0, 0, H, hd], np.int64), "heads_shape")
+    merge_shape = g.const(np.array([0, 0, D], np.int64), "merge_shape")
+    sqrt2 = g.const(np.array(1.4142135381698608, np.float32), "sqrt2")
+    one = g.const(np.array(1.0, np.float32), "one")
+    half = g.const(np.array(0.5, np.float32), "half")
+
+    def linear(inp, name, fin, fout):
+        w = g.init(name + ".weight", _lin(rng, fin, (fin, fout)))
+        b = g.init(name + ".bias", (0.02 * rng.standard_normal(fout)).astype(np.float32))
+        return g.node("Add", [g.node("MatMul", [inp, w], name=name + "/MatMul"), b], name=name + "/Add")
+
+    def ln(inp, name):
+        gw = g.init(name + ".weight", (1.0 + 0.1 * rng.standard_normal(D)).astype(np.float32))
+        gb = g.init(name + ".bias", (0.1 * rng.standard_normal(D)).astype(np.float32))
+        return g.node("LayerNormalization", [inp, gw, gb], name=name, axis=-1, epsilon=1e-5)
+
+    def attention(a, p, layer):
+        q = linear(a, p + "query", D, D)
+        k = linear(a, p + "key", D, D)
+        v = linear(a, p + "value", D, D)
+        q = g.node("Transpose", [g.node("Reshape", [q, heads_shape], name=p + "q_heads")], name=p + "q_perm",
+                   perm=[0, 2, 1, 3])
+        k = g.node("Transpose", [g.node("Reshape", [k, heads_shape], name=p + "k_heads")], name=p + "k_perm",
+                   perm=[0, 2, 3, 1])
+        v = g.node("Transpose", [g.node("Reshape", [v, heads_shape], name=p + "v_heads")], name=p + "v_perm",
+                   perm=[0, 2, 1, 3])
+        sc = score_ops(g, g.node("MatMul", [q, k], name=p + "scores"), p, layer)
+        sc = g.node("Softmax", [sc], name=p + "softmax", axis=-1)
+        c = g.node("MatMul", [sc, v], name=p + "context")
+        c = g.node("Reshape", [g.node("Transpose", [c], name=p + "ctx_perm", perm=[0, 2, 1, 3]), merge_shape],
+                   name=p + "ctx_merge")
+        return linear(c, p + "attn_out", D, D)
+
+    def ffn(a, p):
+        m = linear(a, p + "intermediate", D, F)
+        t = g.node("Div", [m, sqrt2], name=p + "gelu/div")
+        t = g.node("Add", [g.node("Erf", [t], name=p + "gelu/erf"), one], name=p + "gelu/add")
+        t = g.node("Mul", [g.node("Mul", [m, t], name=p + "gelu/mul"), half], name=p + "gelu/half")
+        return linear(t, p + "output", F, D)
+
+    for i in range(s["layers"]):
+        p = "layer%d." % i
+        if pre_ln:  # GPT: x + attn(ln(x)), x + ffn(ln(x))
+            h = g.node("Add", [attention(ln(h, p + "ln1"), p, i), h], name=p + "residual1")
+            h = g.node("Add", [ffn(ln(h, p + "ln2"), p), h], name=p + "residual2")
+        else:
+            h = ln(g.node("Add", [attention(h, p, i), h], name=p + "residual1"), p + "ln1")
+            h = ln(g.node("Add", [ffn(h, p), h], name=p + "residual2"), p + "ln2")
+    if pre_ln:
+        h = ln(h, "ln_f")
+    pooled = g.node("ReduceMean", [h], name="mean_pool", axes=[1], keepdims=0)
+    w = g.init("classifier.weight", _lin(rng, D, (s["classes"], D)))
+    b = g.init("classifier.bias", (0.1 * rng.standard_normal(s["classes"])).astype(np.float32))
+    y = g.node("Gemm", [pooled, w, b], name="classifier", transB=1)
+    g.output(y, ["N", s["classes"]])
+    return g.model_proto(opset=opset), dict(g.initializers)
 
 
 def build_se_cnn(seed: int = 0, opset: int = 13) -> Tuple[bytes, Dict[str, np.ndarray]]:
@@ -396,7 +516,11 @@ BUILDERS = {"mlp": build_mlp, "bert": build_bert, "se_cnn": build_se_cnn, "ratio
             "ln_wide": build_ln_wide, "ln_offset": build_ln_offset,
             "bert_long": lambda seed=0: build_bert(seed, spec="bert_long"),
             "bert_hd32": lambda seed=0: build_bert(seed, spec="bert_hd32"),
-            "bert_hd128": lambda seed=0: build_bert(seed, spec="bert_hd128")}
+            "bert_hd128": lambda seed=0: build_bert(seed, spec="bert_hd128"),
+            "gpt_causal": lambda seed=0: build_masked_encoder(seed, spec="gpt_causal"),
+            "bert_relpos": lambda seed=0: build_masked_encoder(seed, spec="bert_relpos"),
+            "bert_window": lambda seed=0: build_masked_encoder(seed, spec="bert_window"),
+            "bert_keymask": lambda seed=0: build_masked_encoder(seed, spec="bert_keymask")}
 
 
 def build_onnx(name: str, seed: int = 0) -> bytes:
@@ -407,7 +531,7 @@ def input_shape(name: str):
     s = SPECS[name]
     if name in ("mlp", "ratio_mlp"):
         return (s["in_features"],)
-    if name in ("bert", "bert_long", "bert_hd32", "bert_hd128", "token_mixer", "ln_wide", "ln_offset"):
+    if name in ("bert", "bert_long", "bert_hd32", "bert_hd128", "token_mixer", "ln_wide", "ln_offset") + MASKED:
         return (s["seq"] * s["dim"],)
     return (s["in_ch"], s["image"], s["image"])
 

@@ -724,6 +724,8 @@ def _sig_kernels():
     L.die_kern_gather_rows.argtypes = [u64, u64] + [i] * 4 + [u64, i]
     L.die_kern_attention.restype = i
     L.die_kern_attention.argtypes = [u64] * 4 + [i] * 8 + [C.c_float, u64, i]
+    L.die_kern_attention_masked.restype = i
+    L.die_kern_attention_masked.argtypes = [u64] * 4 + [i] * 8 + [C.c_float, u64, i, u64, i, i, i]
     L.die_kern_set_attention_variant.restype = None
     L.die_kern_set_attention_variant.argtypes = [i]
     L.die_kern_set_decode_variant.restype = None

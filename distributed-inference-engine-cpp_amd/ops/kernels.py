@@ -347,9 +347,41 @@ def gather_rows(x, idx, split=False):
     return _out(y, split)
 
 
-def attention(q, k, v, heads, scale=None):
+_LOG2E = 1.4426950408889634
+
+
+def _attention_bias(bias, S, heads):
+    """bias [S, S] or [H, S, S] fp32, natural units -> (the kernel's table [Hb][S][Sp] with Sp = S
+    rounded up to 32, pre-multiplied by log2(e) (the kernel's softmax runs in exp2), Hb, Sp)."""
+    import torch
+
+    if bias.dim() == 2:
+        bias = bias[None]
+    if bias.dim() != 3 or bias.shape[0] not in (1, heads) or tuple(bias.shape[1:]) != (S, S):
+        raise ValueError("attention bias must be [S, S] or [H, S, S] with S = %d, H = %d, got %s"
+                         % (S, heads, tuple(bias.shape)))
+    Sp = (S + 31) // 32 * 32
+    table = torch.zeros((bias.shape[0], S, Sp), dtype=torch.float32, device=bias.device)
+    table[..., :S] = bias.float() * _LOG2E
+    return table, int(bias.shape[0]), Sp
+
+
+def _attention_launch(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, split, bias, causal, what):
+    if bias is None and not causal:  # the unmasked entry point, as before
+        rc = native.kernels().die_kern_attention(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, _stream(), split)
+    else:
+        table, hb, Sp = _attention_bias(bias, S, heads) if bias is not None else (None, 0, 0)
+        rc = native.kernels().die_kern_attention_masked(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, _stream(),
+                                                        split, _ptr(table), hb, Sp, int(bool(causal)))
+    _check(rc, what)
+
+
+def attention(q, k, v, heads, scale=None, bias=None, causal=False):
     """q/k/v: [B, S, H*D] bf16 (may be column slices of a wider tensor, row stride = stride(1)).
-    Returns softmax(scale * Q K^T) V merged back to [B, S, H*D] bf16."""
+    Returns softmax(scale * Q K^T + bias) V merged back to [B, S, H*D] bf16.
+    bias: fp32 [S, S] (shared by the heads) or [H, S, S], natural units, -inf = masked, the same for
+    every image of the batch; causal: key j is visible to query i iff j <= i (on top of any bias).
+    A query row with no visible key at all is undefined (NaN in ONNX): the caller must not pass one."""
     import torch
 
     B, S, C = q.shape
@@ -358,9 +390,8 @@ def attention(q, k, v, heads, scale=None):
         assert t.stride(2) == 1 and t.stride(0) == S * t.stride(1), "rows must be [B*S][ld] with unit column stride"
     out = torch.empty((B, S, C), dtype=torch.bfloat16, device=q.device)
     sc = float(scale if scale is not None else 1.0 / np.sqrt(D))
-    rc = native.kernels().die_kern_attention(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, S, heads, D, q.stride(1),
-                                             k.stride(1), v.stride(1), C, sc, _stream(), 0)
-    _check(rc, "attention")
+    _attention_launch(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, S, heads, D, q.stride(1), k.stride(1), v.stride(1), C,
+                      sc, 0, bias, causal, "attention")
     return out
 
 
@@ -370,9 +401,10 @@ def set_attention_variant(v):
     native.kernels().die_kern_set_attention_variant(int(v))
 
 
-def attention_qkv_split(qkv, heads, scale=None):
+def attention_qkv_split(qkv, heads, scale=None, bias=None, causal=False):
     """fp32 mode: qkv [B, S, 3*C] float (Q | K | V columns) -> fp32 [B, S, C] through the split kernel
-    (planes of the packed QKV rows, like the engine's fused QKV GEMM output)."""
+    (planes of the packed QKV rows, like the engine's fused QKV GEMM output).  bias / causal: as
+    attention() takes them (the bias is fp32 in both precisions)."""
     import torch
 
     B, S, C3 = qkv.shape
@@ -382,9 +414,8 @@ def attention_qkv_split(qkv, heads, scale=None):
     out = torch.empty((2, B, S, C), dtype=torch.bfloat16, device=qkv.device)
     sc = float(scale if scale is not None else 1.0 / np.sqrt(D))
     base = _ptr(planes)
-    rc = native.kernels().die_kern_attention(base, base + 2 * C, base + 4 * C, _ptr(out), B, S, heads, D, C3, C3, C3,
-                                             C, sc, _stream(), 1)
-    _check(rc, "attention (split)")
+    _attention_launch(base, base + 2 * C, base + 4 * C, _ptr(out), B, S, heads, D, C3, C3, C3, C, sc, 1, bias, causal,
+                      "attention (split)")
     return join_planes(out)
 
 

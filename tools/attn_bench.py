@@ -1,11 +1,19 @@
 #!/usr/bin/env python3
 """Streaming-attention variants (kernels.h set_attention_variant: 0 default, 1 K/V two tiles ahead,
-2 without the XCD-aware pair mapping) on ViT-B/16's attention: packed
+2 without the XCD-aware pair mapping) and masked modes on ViT-B/16's attention: packed
 QKV rows [B * 197, 3 * 768] as the fused QKV GEMM writes them, 12 heads of 64, fp32 split mode and
 bf16; each a captured hipGraph of 20 launches, median of 5 trials; outputs checked against the
 default variant (bitwise) and against torch float64.
 
-  python tools/attn_bench.py [--batch 32] [--seq 197] [--md out.md]
+--mask takes a comma-separated list of
+  none        the unmasked kernel (all three variants, as before)
+  bias        one fp32 [S, S] table shared by the heads
+  bias_heads  a per-head [H, S, S] table
+  causal      the causal flag (no table); at long S compare its time to `none`: a block fetches
+              only the key tiles up to its last query and a wave skips the tiles past its own
+The masked modes run the default variant only (they have no two-tiles-ahead instantiation).
+
+  python tools/attn_bench.py [--batch 32] [--seq 197] [--mask none,bias,bias_heads,causal] [--md out.md]
 """
 import argparse
 import os
@@ -14,14 +22,21 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+MASKS = ("none", "bias", "bias_heads", "causal")
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--seq", type=int, default=197)
     ap.add_argument("--heads", type=int, default=12)
+    ap.add_argument("--mask", default="none", help="comma-separated: " + ", ".join(MASKS))
     ap.add_argument("--md", default="")
     a = ap.parse_args()
+    masks = [m for m in a.mask.split(",") if m]
+    for m in masks:
+        if m not in MASKS:
+            ap.error("unknown mask mode %r" % m)
     import numpy as np
     import torch
 
@@ -31,56 +46,80 @@ def main():
 
     B, S, H, D = a.batch, a.seq, a.heads, 64
     C = H * D
+    Sp = (S + 31) // 32 * 32
+    LOG2E = 1.4426950408889634
     qkv = torch.randn(B, S, 3 * C, device="cuda")
     q, k, v = (qkv[..., i * C:(i + 1) * C].double().reshape(B, S, H, D).transpose(1, 2) for i in range(3))
-    ref = torch.softmax(q @ k.transpose(-1, -2) / np.sqrt(D), -1) @ v
-    ref = ref.transpose(1, 2).reshape(B, S, C)
+    scores = q @ k.transpose(-1, -2) / np.sqrt(D)
     L = native.kernels()
-    lines = ["# Streaming attention variants, B=%d S=%d H=%d D=64 (MI355X)" % (B, S, H), "",
-             "| mode | variant | us | rel err vs fp64 | bitwise = variant 0 |", "|---|---:|---:|---:|---|"]
-    for split in (True, False):
-        if split:
-            src = K.split_planes(qkv)  # [2, B, S, 3C] bf16
-            out = torch.empty((2, B, S, C), dtype=torch.bfloat16, device="cuda")
-        else:
-            src = qkv.to(torch.bfloat16).contiguous()
-            out = torch.empty((B, S, C), dtype=torch.bfloat16, device="cuda")
-        base = src.data_ptr()
+    lines = ["# Streaming attention, B=%d S=%d H=%d D=64 (MI355X)" % (B, S, H), "",
+             "| mode | mask | variant | us | rel err vs fp64 | bitwise = variant 0 |", "|---|---|---:|---:|---:|---|"]
+    for mask in masks:
+        # the additive term of the float64 reference and the kernel's table ([Hb][S][Sp], exp2 units)
+        bias_nat = None
+        if mask == "bias":
+            bias_nat = torch.randn(1, S, S, device="cuda")
+        elif mask == "bias_heads":
+            bias_nat = torch.randn(H, S, S, device="cuda")
+        term = bias_nat.double() if bias_nat is not None else 0.0
+        if mask == "causal":
+            i = torch.arange(S, device="cuda")
+            term = torch.where(i[None, :] <= i[:, None], 0.0, -float("inf")).double()
+        ref = (torch.softmax(scores + term, -1) @ v).transpose(1, 2).reshape(B, S, C)
+        table, hb = None, 0
+        if bias_nat is not None:
+            hb = bias_nat.shape[0]
+            table = torch.zeros(hb, S, Sp, device="cuda")
+            table[..., :S] = bias_nat * LOG2E
+        for split in (True, False):
+            if split:
+                src = K.split_planes(qkv)  # [2, B, S, 3C] bf16
+                out = torch.empty((2, B, S, C), dtype=torch.bfloat16, device="cuda")
+            else:
+                src = qkv.to(torch.bfloat16).contiguous()
+                out = torch.empty((B, S, C), dtype=torch.bfloat16, device="cuda")
+            base = src.data_ptr()
 
-        def launch():
-            rc = L.die_kern_attention(base, base + 2 * C, base + 4 * C, out.data_ptr(), B, S, H, D, 3 * C, 3 * C,
-                                      3 * C, C, float(1 / np.sqrt(D)), torch.cuda.current_stream().cuda_stream,
-                                      int(split))
-            assert rc == 0, rc
+            def launch():
+                st = torch.cuda.current_stream().cuda_stream
+                if mask == "none":
+                    rc = L.die_kern_attention(base, base + 2 * C, base + 4 * C, out.data_ptr(), B, S, H, D, 3 * C,
+                                              3 * C, 3 * C, C, float(1 / np.sqrt(D)), st, int(split))
+                else:
+                    rc = L.die_kern_attention_masked(base, base + 2 * C, base + 4 * C, out.data_ptr(), B, S, H, D,
+                                                     3 * C, 3 * C, 3 * C, C, float(1 / np.sqrt(D)), st, int(split),
+                                                     table.data_ptr() if table is not None else 0, hb,
+                                                     Sp if table is not None else 0, int(mask == "causal"))
+                assert rc == 0, rc
 
-        first = None
-        for var in (0, 1, 2):
-            K.set_attention_variant(var)
-            launch()
-            torch.cuda.synchronize()
-            res = (K.join_planes(out) if split else out.float()).clone()
-            err = float((res.double() - ref).norm() / ref.norm())
-            same = "-" if first is None else str(bool(torch.equal(res, first)))
-            if first is None:
-                first = res
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                for _ in range(20):
-                    launch()
-            g.replay()
-            torch.cuda.synchronize()
-            ts = []
-            for _ in range(5):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
+            first = None
+            for var in (0, 1, 2) if mask == "none" else (0,):
+                K.set_attention_variant(var)
+                launch()
+                torch.cuda.synchronize()
+                res = (K.join_planes(out) if split else out.float()).clone()
+                err = float((res.double() - ref).norm() / ref.norm())
+                same = "-" if first is None else str(bool(torch.equal(res, first)))
+                if first is None:
+                    first = res
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    for _ in range(20):
+                        launch()
                 g.replay()
-                e1.record()
-                e1.synchronize()
-                ts.append(e0.elapsed_time(e1) * 1000 / 20)
-            lines.append("| %s | %d | %.2f | %.1e | %s |" % ("fp32 split" if split else "bf16", var,
-                                                              statistics.median(ts), err, same))
-            print(lines[-1], flush=True)
-        K.set_attention_variant(0)
+                torch.cuda.synchronize()
+                ts = []
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    g.replay()
+                    e1.record()
+                    e1.synchronize()
+                    ts.append(e0.elapsed_time(e1) * 1000 / 20)
+                lines.append("| %s | %s | %d | %.2f | %.1e | %s |" % ("fp32 split" if split else "bf16", mask, var,
+                                                                       statistics.median(ts), err, same))
+                print(lines[-1], flush=True)
+            K.set_attention_variant(0)
     if a.md:
         open(a.md, "w").write("\n".join(lines) + "\n")
 
