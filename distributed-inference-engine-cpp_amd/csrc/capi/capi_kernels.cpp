@@ -196,6 +196,28 @@ int die_kern_attention(uint64_t q, uint64_t k, uint64_t v, uint64_t out, int B, 
                                           P<uint16_t>(out), B, Sq, H, D, ldq, ldk, ldv, ldo, scale, S(stream), split));
 }
 
+// Embedding lookup + key data (kernels.h embed_tokens); kvis / kend 0 = no key data
+int die_kern_embed_tokens(uint64_t ids, uint64_t table, int ldt, uint64_t pos, uint64_t type, uint64_t out, int B, int Sq,
+                          int V, int C, uint64_t stream, int split, uint64_t kvis, uint64_t kend, int Sp, int pad_op,
+                          float pad_c, int pad_neg, int pad_trunc) {
+  return static_cast<int>(kern::embed_tokens(P<const float>(ids), P<const float>(table), ldt, P<const float>(pos),
+                                             P<const float>(type), P<uint16_t>(out), B, Sq, V, C, S(stream), split,
+                                             P<float>(kvis), P<int>(kend), Sp, pad_op, pad_c, pad_neg, pad_trunc));
+}
+
+// the kernels' id -> table row rule on the host (k::token_index)
+int die_token_index(float x, int V) { return kern::token_index_host(x, V); }
+
+// die_kern_attention_masked plus the per-sample key mask (kvis [B][Sp] fp32, kend [B] int; 0 = none)
+int die_kern_attention_keymask(uint64_t q, uint64_t k, uint64_t v, uint64_t out, int B, int Sq, int H, int D, int ldq,
+                               int ldk, int ldv, int ldo, float scale, uint64_t stream, int split, uint64_t bias,
+                               int bias_heads, int Sp, int causal, uint64_t kvis, uint64_t kend) {
+  return static_cast<int>(kern::attention(P<const uint16_t>(q), P<const uint16_t>(k), P<const uint16_t>(v),
+                                          P<uint16_t>(out), B, Sq, H, D, ldq, ldk, ldv, ldo, scale, S(stream), split,
+                                          P<const float>(bias), bias_heads, Sp, causal, P<const float>(kvis),
+                                          P<const int>(kend)));
+}
+
 // bias: fp32 [bias_heads][Sq][Sp] pre-multiplied by log2(e) (kernels.h attention), 0 = none
 int die_kern_attention_masked(uint64_t q, uint64_t k, uint64_t v, uint64_t out, int B, int Sq, int H, int D, int ldq,
                               int ldk, int ldv, int ldo, float scale, uint64_t stream, int split, uint64_t bias,
@@ -344,17 +366,18 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
       Json e = Json::object();
       static const char* kinds[] = {"input_prep", "conv", "pool", "gap", "affine", "to_nchw_f32", "bf16_to_f32",
                                     "layernorm", "tokens", "gather_rows", "attention", "stem", "gconv", "softmax",
-                                    "rows_prep", "copy_cols", "binary", "unary", "conv_pair", "pad", "where", "resize", "bmm", "gap_fc"};
-      static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::GAP_FC + 1, "one name per PlanOp kind");
+                                    "rows_prep", "copy_cols", "binary", "unary", "conv_pair", "pad", "where", "resize", "bmm", "gap_fc",
+                                    "embed_tokens"};
+      static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::EMBED_TOKENS + 1, "one name per PlanOp kind");
       e["kind"] = kinds[o.kind];
       e["name"] = o.name;
       e["gflop"] = o.flops_per_sample / 1e9;
       e["join"] = o.join;
       // arena ranges [offset, offset + bytes) at max_batch of the op's buffers, by role
       Json bufs = Json::object();
-      const char* roles[] = {"in", "in2", "in3", "out", "out2", "out3", "out_stats"};
-      const int ids[] = {o.in, o.in2, o.in3, o.out, o.out2, o.out3, o.out_stats};
-      for (int r = 0; r < 7; ++r)
+      const char* roles[] = {"in", "in2", "in3", "out", "out2", "out3", "out_stats", "in4", "in5"};
+      const int ids[] = {o.in, o.in2, o.in3, o.out, o.out2, o.out3, o.out_stats, o.in4, o.in5};
+      for (int r = 0; r < 9; ++r)
         if (ids[r] >= 0) {
           Json range = Json::array();
           range.push_back(static_cast<long long>(p.bufs[ids[r]].offset));
@@ -381,6 +404,7 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
       if (o.kind == PlanOp::ATTENTION) {
         e["bias_heads"] = o.bias_heads;  // 0: no table, 1: one slice shared by the heads, nh: per head
         e["causal"] = o.causal != 0;
+        e["key_mask"] = o.key_mask != 0;  // the request's padding mask (key data from the embed_tokens op)
         if (o.bias_heads) {  // the folded table, back in natural units: sum of its finite entries, count of -inf
           const int Sp = (o.S + 31) / 32 * 32;
           const float* t = reinterpret_cast<const float*>(p.params.data() + o.bias_off);
@@ -394,6 +418,21 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
             }
           e["bias_sum"] = sum / 1.4426950408889634;
           e["bias_masked"] = masked;
+        }
+      }
+      if (o.kind == PlanOp::EMBED_TOKENS) {
+        e["vocab"] = o.gidx;
+        e["seq"] = o.S;
+        e["dim"] = o.Cp;
+        e["positions"] = o.shift_off != SIZE_MAX;
+        e["token_type"] = o.bias_off != SIZE_MAX;
+        e["key_data"] = o.out2 >= 0;
+        if (o.out2 >= 0) {  // visible = ((trunc ? trunc(id) : id) op c) != neg
+          static const char* cmp[] = {"equal", "greater", "less"};
+          e["pad_op"] = cmp[o.act];
+          e["pad_value"] = static_cast<double>(o.clip_lo);
+          e["pad_negated"] = o.is_max != 0;
+          e["pad_truncated"] = o.in_relu != 0;
         }
       }
       if (o.kind == PlanOp::LAYERNORM) e["stats_only"] = o.stats_only != 0;

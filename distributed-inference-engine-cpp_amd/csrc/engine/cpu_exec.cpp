@@ -947,6 +947,15 @@ CpuValuePtr CpuExecutor::run(const CpuValuePtr& input, std::unordered_map<std::s
   if (model_.inputs.empty()) throw std::runtime_error("model has no inputs");
   std::unordered_map<std::string, CpuValuePtr> env;
   env[model_.inputs[0].name] = input;
+  // an input declared INT64 / INT32 (token ids) is fed as floats like any other: truncated here
+  if (!input->is_int && (model_.inputs[0].elem_type == onnx::INT64 || model_.inputs[0].elem_type == onnx::INT32)) {
+    auto ids = std::make_shared<CpuValue>();
+    ids->shape = input->shape;
+    ids->is_int = true;
+    ids->i.resize(input->f.size());
+    for (size_t e = 0; e < input->f.size(); ++e) ids->i[e] = static_cast<int64_t>(input->f[e]);
+    env[model_.inputs[0].name] = ids;
+  }
   const int64_t opset = model_.opset();
   auto get = [&](const std::string& name) -> const CpuValue* {
     if (name.empty()) return nullptr;

@@ -184,6 +184,7 @@ class HipEngine : public Engine {
       HIP_CHECK(hipMalloc(&sl.d_in, sizeof(float) * in_numel_ * max_batch_));
       HIP_CHECK(hipMalloc(&sl.d_out, sizeof(float) * out_numel_ * max_batch_));
       HIP_CHECK(hipMemset(sl.d_in, 0, sizeof(float) * in_numel_ * max_batch_));
+      fill_token_input(sl.d_in);
       HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sl.h_out), sizeof(float) * out_numel_ * max_batch_,
                               hipHostMallocDefault));
       for (auto& ev : sl.ev_h2d) HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -726,6 +727,20 @@ class HipEngine : public Engine {
     j["executors"] = n_exec_;
     j["copy_streams"] = n_copy_streams_;
     j["plan"] = plan_.summary();
+    {  // what a request's numbers are: activations, or token ids looked up in an embedding table
+      const PlanOp* emb = nullptr;
+      for (const PlanOp& op : plan_.ops)
+        if (op.kind == PlanOp::EMBED_TOKENS && !emb) emb = &op;
+      j["input_kind"] = emb ? "token_ids" : "activations";
+      if (emb) {
+        j["vocab"] = emb->gidx;
+        static const char* cmp[] = {"==", ">", "<"};
+        if (emb->out2 >= 0)  // a key is visible where this holds
+          j["pad_compare"] = std::string(emb->is_max ? "not " : "") + (emb->in_relu ? "trunc(id) " : "id ") + cmp[emb->act] +
+                             " " + std::to_string(emb->clip_lo);
+        else j["pad_compare"] = "none";
+      }
+    }
     j["precision"] = sp_ ? "fp32" : "bf16";
     j["gflop_per_image"] = plan_.flops_per_sample / 1e9;
     j["arena_mib"] = static_cast<double>(plan_.arena_bytes) / (1 << 20);
@@ -845,6 +860,33 @@ class HipEngine : public Engine {
       }
       std::rename(tmp.c_str(), path.c_str());
     } catch (const std::exception&) {
+    }
+  }
+
+  // Token-id plans: an all-zero start-up input is all padding under the usual pad id 0, and the
+  // eager validation pass, autotune and the batch curve would time attention with no visible key.
+  // Fill the slot with an in-range id the pad test keeps visible, so they see full-length
+  // sequences; serving inputs overwrite it as before.
+  void fill_token_input(float* d_in) {
+    for (const PlanOp& op : plan_.ops) {
+      if (op.kind != PlanOp::EMBED_TOKENS) continue;
+      float id = 0.f;
+      if (op.out2 >= 0) {
+        bool found = false;
+        for (int c = 0; c < op.gidx && !found; ++c) {  // ids near the compare constant first, then 0, 1, ...
+          for (float t : {op.clip_lo + 1.f + c, op.clip_lo - 1.f - c, static_cast<float>(c)}) {
+            if (t < 0.f || t > static_cast<float>(op.gidx - 1) || t != std::floor(t)) continue;
+            if (kern::token_visible_host(t, op.act, op.clip_lo, op.is_max, op.in_relu)) {
+              id = t;
+              found = true;
+              break;
+            }
+          }
+        }
+      }
+      std::vector<float> h(in_numel_ * max_batch_, id);
+      HIP_CHECK(hipMemcpy(d_in, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+      return;
     }
   }
 
@@ -1462,7 +1504,15 @@ class HipEngine : public Engine {
                               static_cast<const uint16_t*>(buf(op.in3)) + op.col[2], static_cast<uint16_t*>(buf(op.out)),
                               B, op.S, op.nh, op.hd, op.ld[0], op.ld[1], op.ld[2], op.C, op.fscale, st, sp_,
                               op.bias_heads ? prm(op.bias_off) : nullptr, op.bias_heads,
-                              op.bias_heads ? (op.S + 31) / 32 * 32 : 0, op.causal);
+                              op.bias_heads || op.key_mask ? (op.S + 31) / 32 * 32 : 0, op.causal,
+                              op.key_mask ? static_cast<const float*>(buf(op.in4)) : nullptr,
+                              op.key_mask ? static_cast<const int*>(buf(op.in5)) : nullptr);
+          break;
+        case PlanOp::EMBED_TOKENS:
+          e = kern::embed_tokens(static_cast<const float*>(buf(op.in)), prm(op.w_off), op.C, prm(op.shift_off),
+                                 prm(op.bias_off), static_cast<uint16_t*>(buf(op.out)), B, op.S, op.gidx, op.C, st, sp_,
+                                 static_cast<float*>(buf(op.out2)), static_cast<int*>(buf(op.out3)),
+                                 op.out2 >= 0 ? (op.S + 31) / 32 * 32 : 0, op.act, op.clip_lo, op.is_max, op.in_relu);
           break;
         case PlanOp::GCONV: {
           kern::GConvArgs g;
@@ -1543,8 +1593,9 @@ class HipEngine : public Engine {
     for (auto& e : ev) (void)hipEventDestroy(e);
     static const char* kinds[] = {"input_prep", "conv", "pool", "gap", "affine", "to_nchw_f32", "bf16_to_f32",
                                   "layernorm", "tokens", "gather_rows", "attention", "stem", "gconv", "softmax",
-                                  "rows_prep", "copy_cols", "binary", "unary", "conv_pair", "pad", "where", "resize", "bmm", "gap_fc"};
-    static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::GAP_FC + 1, "one name per PlanOp kind");
+                                  "rows_prep", "copy_cols", "binary", "unary", "conv_pair", "pad", "where", "resize", "bmm", "gap_fc",
+                                  "embed_tokens"};
+    static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::EMBED_TOKENS + 1, "one name per PlanOp kind");
     Json out = Json::object();
     Json ops = Json::array();
     double total = 0;
@@ -1568,6 +1619,7 @@ class HipEngine : public Engine {
       if (op.kind == PlanOp::ATTENTION) {
         o["bias_heads"] = op.bias_heads;
         o["causal"] = op.causal != 0;
+        o["key_mask"] = op.key_mask != 0;
       }
       total += us[i];
       ops.push_back(o);

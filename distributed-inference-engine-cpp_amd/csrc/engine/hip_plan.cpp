@@ -52,6 +52,8 @@ struct Val {
     SHAPE,       // int64 shape-computation value (ints known unless `known` is false)
     BCAST_INIT,  // Expand(initializer, shape) -> [B, 1, C]
     TOKCAT,      // Concat([cls, patch rows], axis=1)
+    TOKEN_IDS,   // the rank-2 graph input [N, S] read as token ids (fp32 in the input buffer; H = S)
+    KEYVIS,      // per-key boolean derived from the ids (padding): a pad test, a polarity, a shape
     UNKNOWN      // produced by a node the planner could not lower (support report)
   } kind = NHWC;
   int C = 0, H = 1, W = 1;
@@ -73,6 +75,13 @@ struct Val {
   int q = -1, k = -1, v = -1, stage = 0;
   float scale = 1.f;
   int mask = -1;  // ATTN stage 0/1/2: index of the folded bias / mask table (Planner::masks_), -1 = none
+  bool kmask = false;  // ATTN: the scores carry the request's key mask (PlanOp::key_mask)
+  // TOKEN_IDS: kv_trunc = behind a Cast to an integer type.  KEYVIS: the value is true (additive
+  // form: masked, i.e. <= -1e4) where ((kv_trunc ? trunc(id) : id) OP kv_c) != kv_neg, OP = kv_op
+  // (0 Equal, 1 Greater, 2 Less); kv_rank = 2 [N, S], 3 [N, 1, S], 4 [N, 1, 1, S]
+  int kv_op = 0, kv_rank = 2;
+  float kv_c = 0.f;
+  bool kv_neg = false, kv_trunc = false, kv_add = false;
   // SHAPE / BCAST_INIT / TOKCAT
   std::vector<int64_t> ints;
   bool known = true;
@@ -118,7 +127,9 @@ class Planner {
       }
       // an Add / Where on attention scores whose mask came from an unsupported node is still tried:
       // its own report line says that the mask must be an initializer
-      if (blocked && !attn_mask_node(n)) {
+      // (likewise an embedding Gather on token ids whose table came from an unsupported node: it
+      // says that the table must be an initializer)
+      if (blocked && !attn_mask_node(n) && !(n.op_type == "Gather" && token_node(n))) {
         report_.blocked++;
         mark_unknown(n);
         continue;
@@ -228,6 +239,17 @@ class Planner {
     const size_t r = vi.dims.size();
     for (size_t k = 1; k < r; ++k)
       if (vi.dims[k] <= 0) throw std::runtime_error("input dims must be static except the batch");
+    if (r == 2 && token_input(vi.name)) {  // [N, S] token ids: read in place by EMBED_TOKENS, no ROWS_PREP
+      Val in;
+      in.kind = Val::TOKEN_IDS;
+      in.H = static_cast<int>(vi.dims[1]);
+      in.buf = kBufGraphIn;
+      in.kv_trunc = vi.elem_type == onnx::INT64 || vi.elem_type == onnx::INT32;
+      define(vi.name, in);
+      plan_.input_shape = {1, in.H};
+      plan_.input_numel = static_cast<size_t>(in.H);
+      return;
+    }
     if (r == 4) {
       Val in;
       in.kind = Val::GRAPH_IN;
@@ -284,6 +306,7 @@ class Planner {
   void lower(int idx) {
     const Node& n = m_.nodes[idx];
     const std::string& op = n.op_type;
+    if (token_node(n)) return lower_token_node(idx);
     if (lower_shape_op(idx)) return;
     if (op == "Conv") return n.get_int("group", 1) != 1 ? lower_gconv(idx) : lower_conv(idx);
     if (op == "Gemm" || (op == "MatMul" && is_init(n.in(1)))) return lower_gemm(idx);
@@ -922,6 +945,262 @@ class Planner {
     return true;
   }
 
+  // ---- token-id models: embedding lookup and the request's own key (padding) mask ------------------
+  // A rank-2 graph input [N, S] is a token input when every consumer treats it as ids: an optional
+  // Cast to INT64 / INT32, the indices of a Gather, and the pad tests Equal / Greater / Less against
+  // a scalar initializer -- and at least one Gather reads it (any other rank-2 input plans as rows).
+  // Whether the Gather is one the engine lowers (axis 0, an initializer table) is lower_embed's
+  // business: a token input with a Gather it rejects gives that report line.
+  bool token_input(const std::string& name) const {
+    bool gathered = false;
+    std::vector<std::string> work{name};
+    for (size_t w = 0; w < work.size(); ++w) {
+      if (graph_outputs_.count(work[w])) return false;
+      for (int ci : consumers(work[w])) {
+        const Node& c = m_.nodes[ci];
+        if (c.op_type == "Cast") {
+          const int to = static_cast<int>(c.get_int("to", onnx::FLOAT));
+          if (to != onnx::INT64 && to != onnx::INT32) return false;
+          work.push_back(c.outputs[0]);
+        } else if (c.op_type == "Gather" && c.inputs.size() == 2 && c.in(1) == work[w] && c.in(0) != work[w]) {
+          gathered = true;
+        } else if (c.op_type == "Equal" || c.op_type == "Greater" || c.op_type == "Less") {
+          float f;
+          if (c.inputs.size() != 2 || !scalar_init(c.in(0) == work[w] ? c.in(1) : c.in(0), f)) return false;
+        } else {
+          return false;
+        }
+      }
+    }
+    return gathered;
+  }
+
+  // A node with a token-id or key-visibility operand: lowered by lower_token_node or rejected there
+  // (nothing else in the planner knows these values).
+  bool token_node(const Node& n) const {
+    for (const auto& in : n.inputs) {
+      auto it = vid_.find(in);
+      if (it != vid_.end() && (vals_[it->second].kind == Val::TOKEN_IDS || vals_[it->second].kind == Val::KEYVIS)) return true;
+    }
+    return false;
+  }
+
+  const Val* val_if(const std::string& name, Val::Kind kind) const {
+    auto it = vid_.find(name);
+    return it != vid_.end() && vals_[it->second].kind == kind ? &vals_[it->second] : nullptr;
+  }
+
+  // The first EMBED_TOKENS op of the plan also writes the key data (kvis, kend) every key-masked
+  // attention reads; one pad test per model.
+  int key_op_ = -1;           // index of that op; its out2 / out3 = kvis / kend once a mask uses them
+  bool key_test_set_ = false;
+
+  void lower_token_node(int idx) {
+    const Node& n = m_.nodes[idx];
+    const std::string& op = n.op_type;
+    const std::string who = op + " " + n.name + ": ";
+    if (const Val* ids = n.inputs.empty() ? nullptr : val_if(n.in(0), Val::TOKEN_IDS)) {
+      if (op == "Cast") {
+        const int to = static_cast<int>(n.get_int("to", onnx::FLOAT));
+        if (to != onnx::INT64 && to != onnx::INT32) throw std::runtime_error(who + "token ids cast only to INT64 / INT32");
+        Val o = *ids;
+        o.kv_trunc = true;
+        define(n.outputs[0], o);
+        return;
+      }
+    }
+    if (op == "Gather" && n.inputs.size() == 2 && val_if(n.in(1), Val::TOKEN_IDS)) return lower_embed(idx);
+    if (op == "Equal" || op == "Greater" || op == "Less") {  // pad test roots
+      for (int side = 0; side < 2 && n.inputs.size() == 2; ++side) {
+        const Val* ids = val_if(n.in(side), Val::TOKEN_IDS);
+        float c = 0.f;
+        if (!ids || !scalar_init(n.in(1 - side), c)) continue;
+        Val o;
+        o.kind = Val::KEYVIS;
+        o.H = ids->H;
+        o.kv_op = op == "Equal" ? 0 : (op == "Greater") == (side == 0) ? 1 : 2;  // c > ids = ids < c
+        o.kv_c = c;
+        o.kv_trunc = ids->kv_trunc;
+        define(n.outputs[0], o);
+        return;
+      }
+      throw std::runtime_error(who + "token ids compare only with a scalar initializer");
+    }
+    // consumers on attention scores: Where(vis, scores, f), Where(hidden, f, scores), Add(scores, additive)
+    if (op == "Where" && n.inputs.size() == 3) {
+      const Val* m = val_if(n.in(0), Val::KEYVIS);
+      for (int side = 1; side <= 2 && m; ++side) {
+        const Val* x = val_if(n.in(side), Val::ATTN);
+        if (!x || x->stage != 0) continue;
+        float f = 0.f;
+        if (!scalar_init(n.in(3 - side), f))
+          throw std::runtime_error("Where " + n.name + ": on attention scores the other branch must be a scalar initializer");
+        if (!(f <= -1e4f))
+          throw std::runtime_error("Where " + n.name + ": fill " + std::to_string(f) + " is not a mask (only fills <= -1e4 or "
+                                   "-inf fold into the attention kernel as -inf); a finite fill above -1e4 is not supported");
+        if (m->kv_add) throw std::runtime_error(who + "the condition must be a boolean key mask");
+        return define_key_masked(n, *x, *m, side == 1);
+      }
+    }
+    if (op == "Add" && n.inputs.size() == 2)
+      for (int side = 0; side < 2; ++side) {
+        const Val* m = val_if(n.in(side), Val::KEYVIS);
+        const Val* x = val_if(n.in(1 - side), Val::ATTN);
+        if (!m || !x || x->stage != 0) continue;
+        if (!m->kv_add)
+          throw std::runtime_error(who + "a key mask added to attention scores must be additive (mask * c with c <= -1e4)");
+        return define_key_masked(n, *x, *m, false);  // masked where the value is true
+      }
+    // propagation
+    const Val* m = n.inputs.empty() ? nullptr : val_if(n.in(0), Val::KEYVIS);
+    if (m && !m->kv_add && (op == "Not" || op == "Cast" || op == "Identity")) {
+      Val o = *m;
+      if (op == "Not") o.kv_neg = !o.kv_neg;
+      define(n.outputs[0], o);
+      return;
+    }
+    if (m && op == "Unsqueeze") {
+      std::vector<int64_t> axes = n.get_ints("axes");
+      if (axes.empty() && n.inputs.size() > 1) ints_of(n.in(1), axes);
+      Val o = *m;
+      o.kv_rank = m->kv_rank + static_cast<int>(axes.size());
+      bool ok = !axes.empty() && o.kv_rank <= 4;
+      for (int64_t a : axes) {
+        if (a < 0) a += o.kv_rank;
+        ok = ok && a >= 1 && a <= o.kv_rank - 2;  // the batch stays first, the keys last
+      }
+      if (!ok) throw std::runtime_error(who + "a key mask is unsqueezed only towards [N, 1, 1, S]");
+      define(n.outputs[0], o);
+      return;
+    }
+    if (m && op == "Reshape") {
+      std::vector<int64_t> shp;
+      const bool ok = ints_of(n.in(1), shp) && shp.size() == 4 && (shp[0] == 0 || shp[0] == -1 || shp[0] == kBatchDim) &&
+                      shp[1] == 1 && shp[2] == 1 && (shp[3] == m->H || (shp[3] == -1 && shp[0] != -1));
+      if (!ok) throw std::runtime_error(who + "a key mask is reshaped only to [N, 1, 1, S]");
+      Val o = *m;
+      o.kv_rank = 4;
+      define(n.outputs[0], o);
+      return;
+    }
+    if (op == "Sub" && n.inputs.size() == 2 && scalar_is(n.in(0), 1.f)) {  // 1 - m
+      if (const Val* s = val_if(n.in(1), Val::KEYVIS); s && !s->kv_add) {
+        Val o = *s;
+        o.kv_neg = !o.kv_neg;
+        define(n.outputs[0], o);
+        return;
+      }
+    }
+    if (op == "Mul" && n.inputs.size() == 2)  // m * c, c <= -1e4: the additive form
+      for (int side = 0; side < 2; ++side) {
+        const Val* s = val_if(n.in(side), Val::KEYVIS);
+        float c = 0.f;
+        if (!s || s->kv_add || !scalar_init(n.in(1 - side), c)) continue;
+        if (!(c <= -1e4f))
+          throw std::runtime_error(who + "a key mask times " + std::to_string(c) + " is not a mask (only factors <= -1e4 "
+                                   "fold into the attention kernel as -inf)");
+        Val o = *s;
+        o.kv_add = true;
+        define(n.outputs[0], o);
+        return;
+      }
+    throw std::runtime_error(who + "token ids feed only a Cast to INT64 / INT32, an embedding Gather (axis 0) and the pad "
+                             "tests Equal / Greater / Less, and a key mask derived from them only Not, Cast, Unsqueeze / "
+                             "Reshape to [N, 1, 1, S], Sub(1, m), Mul(m, c <= -1e4) and the Where / Add on attention scores "
+                             "(masked mean pooling and other uses are out of scope)");
+  }
+
+  // Gather(table [V, D] float initializer, ids, axis 0) [+ Add(positions [S, D] / [1, S, D])]
+  // [+ Add(token-type row [D] / [1, 1, D])] -> one EMBED_TOKENS op producing rows [N, S, D].
+  void lower_embed(int idx) {
+    const Node& n = m_.nodes[idx];
+    const Val ids = val(n.in(1), n);
+    if (n.get_int("axis", 0) != 0)
+      throw std::runtime_error("Gather " + n.name + ": token ids index only axis 0 of an embedding table");
+    auto it = m_.initializers.find(n.in(0));
+    if (it == m_.initializers.end())
+      throw std::runtime_error("Gather " + n.name + ": the embedding table " + n.in(0) + " must be an initializer");
+    const onnx::Tensor& t = it->second;
+    if (t.dims.size() != 2 || !onnx::is_float_type(t.dtype) || static_cast<int64_t>(t.f.size()) != t.numel() || t.numel() == 0)
+      throw std::runtime_error("Gather " + n.name + ": the embedding table must be a float [V, D] initializer");
+    const int V = static_cast<int>(t.dims[0]), D = static_cast<int>(t.dims[1]), S = ids.H, Dp = round8(D);
+    auto padded = [&](const std::vector<float>& f, int rows) {  // [rows][D] -> [rows][Dp], pad columns 0
+      std::vector<float> o(static_cast<size_t>(rows) * Dp, 0.f);
+      for (int r = 0; r < rows; ++r)
+        std::copy_n(f.begin() + static_cast<size_t>(r) * D, D, o.begin() + static_cast<size_t>(r) * Dp);
+      return o;
+    };
+    PlanOp p;
+    p.kind = PlanOp::EMBED_TOKENS;
+    p.name = n.name;
+    p.in = kBufGraphIn;
+    p.S = S;
+    p.gidx = V;
+    p.C = Dp;
+    p.Cp = D;
+    p.w_off = push_f32(padded(t.f, V));
+    // the position Add, then the token-type Add, each the value's only reader
+    std::string out = n.outputs[0];
+    for (int step = 0; step < 2; ++step) {
+      const int ci = sole_consumer(out);
+      if (ci < 0 || m_.nodes[ci].op_type != "Add" || m_.nodes[ci].inputs.size() != 2) break;
+      const Node& a = m_.nodes[ci];
+      const std::string& cn = a.in(0) == out ? a.in(1) : a.in(0);
+      auto ct = m_.initializers.find(cn);
+      if (ct == m_.initializers.end() || !onnx::is_float_type(ct->second.dtype)) break;
+      const auto& d = ct->second.dims;
+      const bool is_pos = (d.size() == 2 && d[0] == S && d[1] == D) || (d.size() == 3 && d[0] == 1 && d[1] == S && d[2] == D);
+      const bool is_type = (d.size() == 1 && d[0] == D) || (d.size() == 3 && d[0] == 1 && d[1] == 1 && d[2] == D);
+      if (step == 0 && is_pos) p.shift_off = push_f32(padded(ct->second.f, S));
+      else if (is_type && p.bias_off == SIZE_MAX) p.bias_off = push_f32(padded(ct->second.f, 1));
+      else break;
+      done_[ci] = true;
+      out = a.outputs[0];
+    }
+    p.out = new_buf(static_cast<size_t>(S) * Dp * 2);
+    Val o;
+    o.kind = Val::ROWS_BF16;
+    o.C = Dp;
+    o.cl = Dp != D ? D : 0;
+    o.H = S;
+    o.rank = 3;
+    o.buf = p.out;
+    define(out, o);
+    if (key_op_ < 0) key_op_ = static_cast<int>(plan_.ops.size());
+    add_op(std::move(p));
+  }
+
+  // scores x with the key mask m: visible where m's value is true (vis_when_true) or false.
+  void define_key_masked(const Node& n, const Val& x, const Val& m, bool vis_when_true) {
+    const std::string who = n.op_type + " " + n.name + ": ";
+    if (m.kv_rank != 4)
+      throw std::runtime_error(who + "a key mask on attention scores must have the shape [N, 1, 1, S] (rank " +
+                               std::to_string(m.kv_rank) + " here)");
+    if (m.H != vals_[x.q].H) throw std::runtime_error(who + "the key mask's length is not the attention's");
+    if (key_op_ < 0)
+      throw std::runtime_error(who + "a key mask needs the token embedding (EMBED_TOKENS writes the key data) lowered first");
+    // visible = ((trunc ? trunc(id) : id) OP c) != neg
+    const int neg = (m.kv_neg != !vis_when_true) ? 1 : 0;
+    PlanOp& e = plan_.ops[key_op_];
+    if (!key_test_set_) {
+      key_test_set_ = true;
+      e.act = m.kv_op;
+      e.clip_lo = m.kv_c;
+      e.is_max = neg;
+      e.in_relu = m.kv_trunc ? 1 : 0;
+      const int Sp = (m.H + 31) / 32 * 32;
+      e.out2 = new_buf(static_cast<size_t>(Sp) * 4);  // kvis: fp32 [Sp] per sample
+      e.out3 = new_buf(16);                           // kend: one int per sample
+      plan_.bufs[e.out2].bytes_per_sample = static_cast<size_t>(Sp) * 4;  // (fp32 in both precisions)
+      plan_.bufs[e.out3].bytes_per_sample = 4;
+    } else if (e.act != m.kv_op || e.clip_lo != m.kv_c || e.is_max != neg || e.in_relu != (m.kv_trunc ? 1 : 0)) {
+      throw std::runtime_error(who + "a second, different pad test (one key mask per model: every attention shares the key data)");
+    }
+    Val o = x;
+    o.kmask = true;
+    define(n.outputs[0], o);
+  }
+
   // ---- attention bias / mask folding --------------------------------------------------------------
   // Between Q K^T and the Softmax a chain may hold, besides the scalar Div / Mul, any number of
   // Add(scores, B) and Where(C, scores, f) nodes with B / C initializers broadcastable to
@@ -992,8 +1271,9 @@ class Planner {
     auto it = m_.initializers.find(tname);
     if (it == m_.initializers.end())
       throw std::runtime_error(n.op_type + " " + n.name + ": the attention " + what + " " + tname +
-                               " must be an initializer (masks that depend on the input, and folding a mask the exporter "
-                               "left as a Slice / Cast / ... subgraph of constants, are out of scope)");
+                               " must be an initializer, or a key mask derived from the token ids (see the report line of "
+                               "the node producing it); other masks that depend on the input, and folding a mask the "
+                               "exporter left as a Slice / Cast / ... subgraph of constants, are out of scope");
     const onnx::Tensor& c = it->second;
     const int S = vals_[x.q].H, nh = vals_[x.q].nh;
     const size_t r = c.dims.size();
@@ -1034,7 +1314,7 @@ class Planner {
     if (!kern::attention_supported(q.hd, S) || k.H != S || v.H != S)
       throw std::runtime_error("attention " + name + ": needs head dim 32, 64, 80, 96 or 128 (64 and <= 256 tokens " +
                                "without the streaming kernel)");
-    if (ctx.mask >= 0 && !kern::attention_supported(q.hd, S, true))
+    if ((ctx.mask >= 0 || ctx.kmask) && !kern::attention_supported(q.hd, S, true))
       throw std::runtime_error("attention " + name + ": a bias / mask on the scores needs the streaming attention kernel, "
                                "which this build leaves out");
     PlanOp p;
@@ -1089,6 +1369,14 @@ class Planner {
       }
       p.causal = causal ? 1 : 0;
       if (causal) p.flops_per_sample = 4.0 * q.hd * q.nh * (static_cast<double>(S) * (S + 1) / 2);
+    }
+    if (ctx.kmask) {  // the request's key mask: the key data the first EMBED_TOKENS op writes
+      if (p.causal)
+        throw std::runtime_error("attention " + name + ": a key (padding) mask together with a causal mask is not "
+                                 "supported (a left-padded causal row has no visible key)");
+      p.key_mask = 1;
+      p.in4 = plan_.ops[key_op_].out2;
+      p.in5 = plan_.ops[key_op_].out3;
     }
     p.out = new_buf(static_cast<size_t>(S) * C * 2);
     const int buf = p.out;
@@ -1315,6 +1603,8 @@ class Planner {
       const Val& x = vals_[vid_.at(n.in(0))];
       if (x.kind == Val::ATTN && x.stage == 0 && it != m_.initializers.end() && it->second.f.size() == 1) {
         Val o = x;
+        if (x.kmask && !(it->second.f[0] > 0.f))
+          throw std::runtime_error(n.op_type + " " + n.name + ": a scale after a key mask must be positive");
         o.scale = n.op_type == "Div" ? x.scale / it->second.f[0] : x.scale * it->second.f[0];
         if (x.mask >= 0) {  // a scale after an Add / Where reaches the accumulated bias as well
           AttnTable t = masks_[x.mask];
@@ -2872,11 +3162,11 @@ class Planner {
       const PlanOp& p = plan_.ops[i];
       for (int b : {p.out, p.out2, p.out3, p.out_stats})
         if (b >= 0 && plan_.bufs[b].first_use < 0) plan_.bufs[b].first_use = i;
-      for (int b : {p.in, p.in2, p.in3, p.out, p.out2, p.out3, p.out_stats})
+      for (int b : {p.in, p.in2, p.in3, p.in4, p.in5, p.out, p.out2, p.out3, p.out_stats})
         if (b >= 0) plan_.bufs[b].last_use = std::max(plan_.bufs[b].last_use, i);
       // a side branch may still be reading its inputs until its join
       if (p.join >= 0)
-        for (int b : {p.in, p.in2, p.in3})
+        for (int b : {p.in, p.in2, p.in3, p.in4, p.in5})
           if (b >= 0) plan_.bufs[b].last_use = std::max(plan_.bufs[b].last_use, p.join);
     }
     // Offsets: greedy by size (largest first, each at the lowest offset that does not overlap an

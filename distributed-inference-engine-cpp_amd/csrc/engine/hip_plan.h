@@ -22,8 +22,18 @@
 //    shared slice, an all-zero remainder no table at all (causal masks, relative-position / ALiBi
 //    tables, BERT key masks, sliding windows).  Rejected with a report line: shapes that do not
 //    broadcast, a finite fill above -1e4, a query row with no visible key, and a mask that is not an
-//    initializer -- masks that depend on the input (there is no second graph input), folding of
-//    mask-building Slice / Cast subgraphs, cross-attention and KV caches are out of scope.
+//    initializer -- folding of mask-building Slice / Cast subgraphs, cross-attention and KV caches
+//    are out of scope.
+//  * token-id models: a rank-2 input [N, S] whose consumers all treat it as ids (Cast to an integer
+//    type, Gather indices, Equal / Greater / Less against a scalar) gets no ROWS_PREP;
+//    Gather(table, ids, axis 0) [+ Add(positions)] [+ Add(token-type row)] is one EMBED_TOKENS op
+//    reading the fp32 input in place, and a padding mask derived from the ids (a pad test through
+//    Not / Cast / Unsqueeze / Reshape / Sub(1, m) / Mul(m, c <= -1e4)) consumed on attention scores
+//    as Where(vis, scores, f), Where(hidden, f, scores) or Add(scores, additive) becomes the
+//    attention op's key_mask flag: EMBED_TOKENS writes the per-sample key data once per forward.
+//    Rejected with a report line: key mask + causal, a visibility value used elsewhere (masked
+//    mean pooling), Gather on another axis or from a non-initializer table, mask shapes other than
+//    [N, 1, 1, S].  A second graph input (attention_mask / token_type_ids tensors) is out of scope.
 //    Sibling Q/K/V MatMuls become one GEMM (N = 3*D); MatMul -> Add(bias) -> erf-GELU and
 //    MatMul -> Add(bias) -> Add(residual) fold into the GEMM epilogue; cls Expand/Concat + position
 //    Add -> one token-assembly kernel; LayerNormalization and Gather(token) -> row kernels.
@@ -66,8 +76,13 @@ struct PlanOp {
              // clip_lo / clip_hi = scales (output / input)
     BMM,     // batched MatMul of two row activations: out [S][Cp pitch C] = in [S][gidx of ld[0]] x
              // in2 [gidx][ld[1]]; Cp = logical N
-    GAP_FC   // global pool (gidx = mode) of in [H*W][C] + the 1x1 GEMM that is its only reader, in one
+    GAP_FC,  // global pool (gidx = mode) of in [H*W][C] + the 1x1 GEMM that is its only reader, in one
              // launch: out_f32 [Cp] = act(pool . w + bias); conv describes the GEMM (Kpad, wplane)
+    EMBED_TOKENS  // token ids (the fp32 graph input [S], in = -2) -> rows: out [S][C] = table[idx(id)] + pos + type
+                  // with w_off = table [gidx = V][C] f32, shift_off = pos [S][C], bias_off = type [C] (C = stored
+                  // width, Cp = the model's); key data for key-masked attention when out2 >= 0: out2 = kvis
+                  // f32 [S rounded up to 32], out3 = kend (one int), pad test visible = ((in_relu ? trunc(id)
+                  // : id) OP clip_lo) != is_max with OP = act (0 Equal, 1 Greater, 2 Less)
   } kind;
   std::string name;
   // buffers (-1 = none).  -2 = the graph input (f32 NCHW), -3 = the graph output (f32).
@@ -96,6 +111,9 @@ struct PlanOp {
   // the kernel's exp2 units (kern::attention), bias_heads = 0 (none), 1 (shared) or nh; causal = 1:
   // key j visible to query i iff j <= i
   int bias_heads = 0, causal = 0;
+  // ATTENTION with the request's key (padding) mask: in4 / in5 = the kvis / kend buffers of the plan's
+  // EMBED_TOKENS op (kern::attention); combines with a bias table, never with causal
+  int key_mask = 0, in4 = -1, in5 = -1;
   double flops_per_sample = 0;
   // Side branch: this op may run on a second stream, concurrently with the ops after it, until
   // op `join` (its first consumer) waits for it.  The arena keeps its inputs live until `join`.

@@ -120,6 +120,25 @@ __device__ __forceinline__ void store1v(uint16_t* p, long long plane, bool split
   }
 }
 
+// Token id carried as a float -> row of a [V][...] table: truncated toward zero and clamped to
+// [0, V - 1]; NaN, negatives and -0 give 0, +inf and anything >= V - 1 give V - 1.  Defined for
+// every bit pattern (rows of a graph bucket past the live batch hold stale input), so a lookup
+// through it is always in bounds.
+__host__ __device__ __forceinline__ int token_index(float x, int V) {
+  if (!(x > 0.f)) return 0;
+  if (x >= static_cast<float>(V - 1)) return V - 1;
+  return static_cast<int>(x);
+}
+
+// Pad test on a token id: (x OP c) != neg with OP = 0 Equal, 1 Greater, 2 Less; trunc: on the id
+// truncated toward zero (the test sits behind the graph's Cast to an integer type).  NaN compares
+// false.  True = the key is visible.
+__host__ __device__ __forceinline__ bool token_visible(float x, int op, float c, int neg, int trunc) {
+  if (trunc) x = truncf(x);
+  const bool t = op == 0 ? x == c : op == 1 ? x > c : x < c;
+  return t != (neg != 0);
+}
+
 // Cross-lane moves on the VALU (DPP), no LDS round trip (ds_bpermute, which __shfl_xor compiles to,
 // puts a dependent LDS latency on every exchange).  CTRL: quad_perm [1,0,3,2] = 0xB1 (lane ^ 1),
 // [2,3,0,1] = 0x4E (lane ^ 2); row_half_mirror = 0x141 (lane i <-> 7-i within each 8 lanes).

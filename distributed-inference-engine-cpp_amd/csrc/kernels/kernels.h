@@ -379,12 +379,32 @@ hipError_t gather_rows(const uint16_t* x, uint16_t* y, int B, int S, int idx, in
 //    the kernel's softmax runs in exp2 and adds the table to score * scale * log2(e) as it is;
 //    -inf = masked;
 //  * causal != 0: key j is visible to query i iff j <= i (from indices; combines with a bias).
-// A query row with no visible key at all is undefined (ONNX gives NaN): callers reject such masks.
-// Wrong bias_heads / Sp / alignment, or a mask on a build without the streaming kernel:
-// hipErrorInvalidValue, nothing launched.
+//  * kvis / kend (both or neither): the per-sample key mask embed_tokens() writes -- kvis [B][Sp]
+//    fp32, 0 = visible, -inf = padding (columns >= S: -inf), 16-byte aligned; kend [B] = 1 + the last
+//    visible key.  A block walks only the key tiles below kend[b].  Combines with a bias, not with
+//    causal.  A sample with kend = 0 gets all-zero rows (ONNX: NaN).
+// A query row with no visible key at all is otherwise undefined (ONNX gives NaN): callers reject
+// such constant masks.
+// Wrong bias_heads / Sp / alignment, a key mask together with causal, or a mask on a build without
+// the streaming kernel: hipErrorInvalidValue, nothing launched.
 hipError_t attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, int B, int S, int H,
                      int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t s, int split = 0,
-                     const float* bias = nullptr, int bias_heads = 0, int Sp = 0, int causal = 0);
+                     const float* bias = nullptr, int bias_heads = 0, int Sp = 0, int causal = 0,
+                     const float* kvis = nullptr, const int* kend = nullptr);
+// Embedding lookup on fp32 token ids [B][S]: out[b, s, :] = table[idx(ids[b, s])] + pos[s] + type,
+// summed in fp32, stored as bf16 rows [B*S][C] (split: hi / lo planes).  idx = k::token_index
+// (common.h): truncate, clamp to [0, V - 1], NaN -> 0 -- never out of bounds, whatever the input
+// holds.  table: [V] rows of pitch ldt >= C (ldt % 4 == 0), pos (nullable) [S][C], type (nullable)
+// [C]; C % 8 == 0 is the stored width, whose pad columns hold 0 in all three; all 16-byte aligned.
+// kvis / kend (both or neither): the key data of attention()'s key mask, from the pad test
+// visible = ((trunc ? trunc(id) : id) OP pad_c) != pad_neg, OP = 0 Equal, 1 Greater, 2 Less;
+// Sp = S rounded up to 32.  One launch.
+hipError_t embed_tokens(const float* ids, const float* table, int ldt, const float* pos, const float* type,
+                        uint16_t* out, int B, int S, int V, int C, hipStream_t s, int split = 0, float* kvis = nullptr,
+                        int* kend = nullptr, int Sp = 0, int pad_op = 0, float pad_c = 0.f, int pad_neg = 1,
+                        int pad_trunc = 0);
+int token_index_host(float x, int V);  // k::token_index on the host (tests)
+bool token_visible_host(float x, int op, float c, int neg, int trunc);  // k::token_visible on the host
 
 }  // namespace kern
 }  // namespace die

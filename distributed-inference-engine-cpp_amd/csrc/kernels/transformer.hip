@@ -210,6 +210,58 @@ __global__ void gather_rows_kernel(const uint16_t* __restrict__ x, uint16_t* __r
   }
 }
 
+// Embedding lookup on token ids carried as fp32 (the graph input itself, never a bf16 copy: a bf16
+// id has 8 significant bits): out[b, s, :] = table[token_index(ids[b, s])] + pos[s] + type, summed in
+// fp32, stored bf16 or split.  table rows have pitch ldt (>= C, % 4 == 0), pos rows and type pitch /
+// length C = the stored width (the model's width rounded up to 8, pad columns 0 in all three, so
+// the output's pad columns are 0); a thread moves 8 columns: two 16-B loads per operand, one 16-B
+// store per plane.  Blocks [0, eblocks) do this, grid-stride.
+// The last B blocks (kvis != nullptr) write the per-sample key data the attention KEYMASK mode
+// reads, block eblocks + b for sample b: kvis[b][j] = 0 where token_visible(ids[b, j]) else -inf
+// (j >= S: -inf) for j < Sp, and kend[b] = 1 + the last visible key (0: none).
+__global__ __launch_bounds__(256) void embed_tokens_kernel(
+    const float* __restrict__ ids, const float* __restrict__ table, int ldt, const float* __restrict__ pos,
+    const float* __restrict__ type, uint16_t* __restrict__ out, int B, int S, int V, int C, int split, int eblocks,
+    float* __restrict__ kvis, int* __restrict__ kend, int Sp, int pad_op, float pad_c, int pad_neg, int pad_trunc) {
+  if (static_cast<int>(blockIdx.x) >= eblocks) {
+    const int b = blockIdx.x - eblocks;  // < B by the launch
+    __shared__ int wmax[4];
+    int last = 0;
+    for (int j = threadIdx.x; j < Sp; j += 256) {
+      const bool vis = j < S && token_visible(ids[static_cast<long long>(b) * S + j], pad_op, pad_c, pad_neg, pad_trunc);
+      kvis[static_cast<long long>(b) * Sp + j] = vis ? 0.f : -INFINITY;
+      if (vis) last = j + 1;  // j ascends per thread
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = last;
+    __syncthreads();
+    if (threadIdx.x == 0) kend[b] = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+    return;
+  }
+  const int CG = C / 8;
+  const long long total = static_cast<long long>(B) * S * CG;
+  const long long plane = static_cast<long long>(B) * S * C;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += static_cast<long long>(eblocks) * 256) {
+    const int cg = static_cast<int>(i % CG);
+    const long long r = i / CG;
+    const int s = static_cast<int>(r % S);
+    const float* trow = table + static_cast<long long>(token_index(ids[r], V)) * ldt + cg * 8;
+    const float4 t0 = *reinterpret_cast<const float4*>(trow), t1 = *reinterpret_cast<const float4*>(trow + 4);
+    float v[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+    if (pos) {
+      const float* p = pos + static_cast<long long>(s) * C + cg * 8;
+      const float4 p0 = *reinterpret_cast<const float4*>(p), p1 = *reinterpret_cast<const float4*>(p + 4);
+      v[0] += p0.x, v[1] += p0.y, v[2] += p0.z, v[3] += p0.w, v[4] += p1.x, v[5] += p1.y, v[6] += p1.z, v[7] += p1.w;
+    }
+    if (type) {
+      const float4 y0 = *reinterpret_cast<const float4*>(type + cg * 8), y1 = *reinterpret_cast<const float4*>(type + cg * 8 + 4);
+      v[0] += y0.x, v[1] += y0.y, v[2] += y0.z, v[3] += y0.w, v[4] += y1.x, v[5] += y1.y, v[6] += y1.z, v[7] += y1.w;
+    }
+    store8v(out + i * 8, plane, split != 0, v);
+  }
+}
+
 // ---- fused attention ------------------------------------------------------------------------------
 // FlashAttention-style, on v_mfma_f32_32x32x16_bf16, for head dim 64 and S <= 256 (ViT: 197 tokens).
 // A block = one (image b, head h) pair, 8 waves (two per SIMD); wave w owns query tile w (32 queries).
@@ -424,9 +476,10 @@ struct AttnGeom {
   // Masked modes: the tile's 16 bias values (and the causal compares) are live across the K Q^T
   // MFMAs; the split instantiations that would spill at the bound above get one wave less
   // (resource figures: profiles/attention_masked.md).
-  static constexpr int waves_per_simd(bool bias, bool causal) {
-    if (!SPLIT || !(bias || causal)) return WAVES_PER_SIMD;
-    return HD == 64 ? 2 : HD == 80 || (HD == 96 && bias) ? 1 : WAVES_PER_SIMD;
+  // (keymask holds its tile's 16 values like bias; with both, the two are summed on arrival)
+  static constexpr int waves_per_simd(bool bias, bool causal, bool keymask = false) {
+    if (!SPLIT || !(bias || causal || keymask)) return WAVES_PER_SIMD;
+    return HD == 64 ? 2 : HD == 80 || (HD == 96 && (bias || keymask)) ? 1 : WAVES_PER_SIMD;
   }
 };
 
@@ -441,14 +494,23 @@ struct AttnGeom {
 //  * CAUSAL: key j visible to query i iff j <= i.  A block walks only the tiles up to its last
 //    query; a wave skips the math of tiles past its own queries (it still stages K/V and meets the
 //    barriers, like an idle wave); the diagonal tile masks per element.
+//  * KEYMASK: a per-sample key mask from the request itself (padding): kvis [B][Sp] fp32 rows of 0
+//    (visible) or -inf (columns >= S: -inf) and kend [B] = 1 + the last visible key, both written by
+//    embed_tokens_kernel in the same forward.  The block walks only the tiles below kend[b]
+//    (block-uniform, like the causal limit); a lane's 16 keys of a tile are four 16-B loads of the
+//    sample's row, issued where the BIAS loads are and added to them on arrival.  Holes inside the
+//    walked tiles are masked per element by the row.  kend[b] = 0 (no visible key): the sample's
+//    rows are written 0 (ONNX gives NaN).  Never together with CAUSAL.
 // A tile can be all -inf for a row while the row's running max is still -inf (a band mask from
 // query 32 on): the masked modes subtract 0 instead of that max, so p = alpha = 0 and o, l stay 0
 // until the row's first visible key.  A row with NO visible key is undefined (callers reject it).
-template <bool SPLIT, bool DEEP, int HD, bool BIAS = false, bool CAUSAL = false>
-__global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAUSAL))) void attention_stream_kernel(
+template <bool SPLIT, bool DEEP, int HD, bool BIAS = false, bool CAUSAL = false, bool KEYMASK = false>
+__global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAUSAL, KEYMASK))) void attention_stream_kernel(
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ v,
     uint16_t* __restrict__ out, int S, int ldq, int ldk, int ldv, int ldo, float scale_log2, int xcd_map,
-    const float* __restrict__ bias, long long bias_hs, int Sp) {
+    const float* __restrict__ bias, long long bias_hs, int Sp, const float* __restrict__ kvis,
+    const int* __restrict__ kend) {
+  static_assert(!(KEYMASK && CAUSAL), "a key mask never combines with the causal flag");
   using G = AttnGeom<HD, SPLIT>;
   constexpr int NP = SPLIT ? 2 : 1;
   constexpr int KT = 32;  // keys per tile
@@ -483,7 +545,13 @@ __global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAU
   const long long rowbase = static_cast<long long>(b) * S;
   const long long rows = static_cast<long long>(gridDim.z) * S;  // plane distances: rows x pitch
   // CAUSAL: the block's last query sees keys below min(S, 128 qblk + 128) only (block-uniform)
-  const int nkt = ((CAUSAL && qblk * 128 + 128 < S ? qblk * 128 + 128 : S) + KT - 1) / KT;
+  int klim = CAUSAL && qblk * 128 + 128 < S ? qblk * 128 + 128 : S;
+  // KEYMASK: keys from kend[b] on are padding (block-uniform; clamped: the value is device data)
+  if constexpr (KEYMASK) {
+    const int ke = kend[b];
+    klim = ke < 0 ? 0 : ke < S ? ke : S;
+  }
+  const int nkt = (klim + KT - 1) / KT;
   // tile loader: load j of a thread = (key row, 16-B chunk) index tid + 256 j of every tensor plane
   typedef uint4 Stage[NP][LPT];
   Stage kr0, vr0, kr1, vr1;
@@ -548,6 +616,9 @@ __global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAU
   const float* brow = nullptr;
   if constexpr (BIAS)
     brow = bias + h * bias_hs + static_cast<long long>(q0 + r < S ? q0 + r : S - 1) * Sp + 4 * hh;
+  // KEYMASK: the sample's visibility row, at this lane half's first key of a tile
+  const float* krow = nullptr;
+  if constexpr (KEYMASK) krow = kvis + static_cast<long long>(b) * Sp + 4 * hh;
   // one key tile; (ka, va): the register set free for a new fetch, (kb, vb): tile kt+1 when DEEP
   auto step = [&](int kt, Stage& ka, Stage& va, Stage& kb, Stage& vb) {
     const int buf = kt & 1;
@@ -566,6 +637,16 @@ __global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAU
       if (does) {
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) bv[g4] = *reinterpret_cast<const float4*>(brow + kt * KT + 8 * g4);
+      }
+    }
+    if constexpr (KEYMASK) {  // same place, same wait; with a BIAS the two terms are summed here
+      if (does) {
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const float4 kv = *reinterpret_cast<const float4*>(krow + kt * KT + 8 * g4);
+          if constexpr (BIAS) bv[g4] = make_float4(bv[g4].x + kv.x, bv[g4].y + kv.y, bv[g4].z + kv.z, bv[g4].w + kv.w);
+          else bv[g4] = kv;
+        }
       }
     }
     if (does) {
@@ -589,7 +670,7 @@ __global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAU
       if (kt * KT + KT <= S && !diag) {  // full tile (wave-uniform): no key mask
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          if constexpr (BIAS) sc[i] = fmaf(sc[i], scale_log2, bv[i >> 2][i & 3]);
+          if constexpr (BIAS || KEYMASK) sc[i] = fmaf(sc[i], scale_log2, bv[i >> 2][i & 3]);
           else sc[i] *= scale_log2;
           mt = fmaxf(mt, sc[i]);
         }
@@ -598,8 +679,8 @@ __global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAU
         for (int i = 0; i < 16; ++i) {
           const int key = kt * KT + (i & 3) + 8 * (i >> 2) + 4 * hh;
           float x;
-          if constexpr (BIAS || CAUSAL) {
-            if constexpr (BIAS) x = fmaf(sc[i], scale_log2, bv[i >> 2][i & 3]);
+          if constexpr (BIAS || CAUSAL || KEYMASK) {
+            if constexpr (BIAS || KEYMASK) x = fmaf(sc[i], scale_log2, bv[i >> 2][i & 3]);
             else x = sc[i] * scale_log2;
             if (!(key < S && (!diag || key <= q0 + r))) x = -INFINITY;
           } else {
@@ -613,7 +694,7 @@ __global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAU
       float mn = fmaxf(m, mt);
       const float mkeep = mn;
       // BIAS: every key so far masked (mn = -inf) -> subtract 0: alpha = p = 0, no inf - inf
-      if constexpr (BIAS) mn = mn == -INFINITY ? 0.f : mn;
+      if constexpr (BIAS || KEYMASK) mn = mn == -INFINITY ? 0.f : mn;
       const float alpha = __builtin_amdgcn_exp2f(m - mn);  // m = -inf on the first tile: 0
       l *= alpha;
 #pragma unroll
@@ -668,7 +749,8 @@ __global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAU
   l += __shfl_xor(l, 32, 64);
   const int qr = q0 + r;
   if (qr >= S) return;
-  const float inv = 1.f / l;
+  // KEYMASK: a row without a visible key (an all-pad sample: no tile walked, o = l = 0) is written 0
+  const float inv = KEYMASK && l == 0.f ? 0.f : 1.f / l;
   uint16_t* orow = out + (rowbase + qr) * ldo + h * HD;
   const long long oplane = rows * ldo;
 #pragma unroll
@@ -784,6 +866,24 @@ hipError_t gather_rows(const uint16_t* x, uint16_t* y, int B, int S, int idx, in
   return hipGetLastError();
 }
 
+int token_index_host(float x, int V) { return token_index(x, V); }
+bool token_visible_host(float x, int op, float c, int neg, int trunc) { return token_visible(x, op, c, neg, trunc); }
+
+hipError_t embed_tokens(const float* ids, const float* table, int ldt, const float* pos, const float* type,
+                        uint16_t* out, int B, int S, int V, int C, hipStream_t s, int split, float* kvis, int* kend,
+                        int Sp, int pad_op, float pad_c, int pad_neg, int pad_trunc) {
+  auto misaligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; };
+  if (B <= 0 || S <= 0 || V <= 0 || C <= 0 || C % 8 || ldt < C || ldt % 4 || !ids || !table || !out ||
+      misaligned(table) || misaligned(pos) || misaligned(type) || misaligned(out))
+    return hipErrorInvalidValue;
+  if ((kvis == nullptr) != (kend == nullptr)) return hipErrorInvalidValue;
+  if (kvis && (Sp != (S + 31) / 32 * 32 || misaligned(kvis) || pad_op < 0 || pad_op > 2)) return hipErrorInvalidValue;
+  const int eblocks = grid_for(static_cast<long long>(B) * S * (C / 8));
+  hipLaunchKernelGGL(embed_tokens_kernel, dim3(eblocks + (kvis ? B : 0)), dim3(256), 0, s, ids, table, ldt, pos, type,
+                     out, B, S, V, C, split, eblocks, kvis, kend, Sp, pad_op, pad_c, pad_neg, pad_trunc);
+  return hipGetLastError();
+}
+
 hipError_t softmax_rows(const uint16_t* x, uint16_t* y, float* y_f32, long long rows, int C, hipStream_t s,
                         int split, int ld) {
   if (ld <= 0) ld = C;
@@ -808,8 +908,8 @@ void set_attention_variant(int v) { g_attn_variant = v; }
 
 hipError_t attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, int B, int S, int H,
                      int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t s, int split,
-                     const float* bias, int bias_heads, int Sp, int causal) {
-  const bool masked = bias != nullptr || causal != 0;
+                     const float* bias, int bias_heads, int Sp, int causal, const float* kvis, const int* kend) {
+  const bool masked = bias != nullptr || causal != 0 || kvis != nullptr;
   if (!attention_supported(D, S, masked) || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4) return hipErrorInvalidValue;
   if (bias) {  // [1 or H][S][Sp] fp32, rows of Sp = S rounded up to 32 (16-byte loads, in bounds in the last tile)
     if ((bias_heads != 1 && bias_heads != H) || Sp != (S + 31) / 32 * 32 || reinterpret_cast<uintptr_t>(bias) % 16)
@@ -817,6 +917,11 @@ hipError_t attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, ui
   } else if (bias_heads != 0) {
     return hipErrorInvalidValue;
   }
+  // key mask: kvis [B][Sp] fp32 (16-byte loads) + kend [B], both or neither, never with causal
+  if ((kvis == nullptr) != (kend == nullptr)) return hipErrorInvalidValue;
+  if (kvis && (causal || Sp != (S + 31) / 32 * 32 || reinterpret_cast<uintptr_t>(kvis) % 16 ||
+               reinterpret_cast<uintptr_t>(kend) % 4))
+    return hipErrorInvalidValue;
   const float sl2 = scale * 1.4426950408889634f;  // softmax in exp2
   if (kAttnStream) {  // 4-wave blocks of 128 queries, K/V streamed in 32-key tiles (any S)
     dim3 grid((S + 127) / 128, H, B);
@@ -825,18 +930,22 @@ hipError_t attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, ui
     const int xcd_map = g_attn_variant == 2 ? 0 : g_attn_variant == 3 ? 2 : 1;
     if (masked) {  // one-tile-ahead staging only (the DEEP measurement variant stays unmasked)
       const long long bias_hs = bias && bias_heads == H && H > 1 ? static_cast<long long>(S) * Sp : 0;
-#define ATTN_MASKED(SP, HDV, BI, CA)                                                                                 \
-  hipLaunchKernelGGL((attention_stream_kernel<SP, false, HDV, BI, CA>), grid, dim3(256), 0, s, q, k, v, out, S, ldq, ldk, \
-                     ldv, ldo, sl2, xcd_map, bias, bias_hs, Sp)
-#define ATTN_MASKED_HD(HDV)                                     \
-  if (split) {                                                  \
-    if (bias && causal) ATTN_MASKED(true, HDV, true, true);     \
-    else if (bias) ATTN_MASKED(true, HDV, true, false);         \
-    else ATTN_MASKED(true, HDV, false, true);                   \
-  } else {                                                      \
-    if (bias && causal) ATTN_MASKED(false, HDV, true, true);    \
-    else if (bias) ATTN_MASKED(false, HDV, true, false);        \
-    else ATTN_MASKED(false, HDV, false, true);                  \
+#define ATTN_MASKED(SP, HDV, BI, CA, KM)                                                                             \
+  hipLaunchKernelGGL((attention_stream_kernel<SP, false, HDV, BI, CA, KM>), grid, dim3(256), 0, s, q, k, v, out, S, ldq, \
+                     ldk, ldv, ldo, sl2, xcd_map, bias, bias_hs, Sp, kvis, kend)
+#define ATTN_MASKED_HD(HDV)                                            \
+  if (split) {                                                         \
+    if (kvis && bias) ATTN_MASKED(true, HDV, true, false, true);       \
+    else if (kvis) ATTN_MASKED(true, HDV, false, false, true);         \
+    else if (bias && causal) ATTN_MASKED(true, HDV, true, true, false); \
+    else if (bias) ATTN_MASKED(true, HDV, true, false, false);         \
+    else ATTN_MASKED(true, HDV, false, true, false);                   \
+  } else {                                                             \
+    if (kvis && bias) ATTN_MASKED(false, HDV, true, false, true);      \
+    else if (kvis) ATTN_MASKED(false, HDV, false, false, true);        \
+    else if (bias && causal) ATTN_MASKED(false, HDV, true, true, false); \
+    else if (bias) ATTN_MASKED(false, HDV, true, false, false);        \
+    else ATTN_MASKED(false, HDV, false, true, false);                  \
   }
       switch (D) {
         case 32: ATTN_MASKED_HD(32) break;
@@ -851,7 +960,8 @@ hipError_t attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, ui
     }
 #define ATTN_LAUNCH(SP, DP, HDV)                                                                                   \
   hipLaunchKernelGGL((attention_stream_kernel<SP, DP, HDV>), grid, dim3(256), 0, s, q, k, v, out, S, ldq, ldk, ldv, ldo, \
-                     sl2, xcd_map, static_cast<const float*>(nullptr), 0LL, 0)
+                     sl2, xcd_map, static_cast<const float*>(nullptr), 0LL, 0, static_cast<const float*>(nullptr),    \
+                     static_cast<const int*>(nullptr))
 #define ATTN_HD(HDV)                          \
   if (split && deep) ATTN_LAUNCH(true, true, HDV);    \
   else if (split) ATTN_LAUNCH(true, false, HDV);      \

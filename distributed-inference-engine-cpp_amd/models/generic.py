@@ -39,7 +39,15 @@ mix a ResNet / ViT never exercises, random weights, written by the in-tree ONNX 
 * `bert_window` a shared band mask (0 inside |i - j| <= 8, -inf outside) added BEFORE the scale, 72
               tokens: from row 41 on the first 32-key tile is entirely masked.
 * `bert_keymask` the BERT extended attention mask: Add of [1, 1, 1, S] with -10000 on the last 9 keys.
-`synthetic_input(model, batch)` gives inputs of the right shape.  The CPU executor is the fp32
+* `bert_ids`   a token-id model: input [N, 48] of ids (vocab 1000, pad id 0), Gather from the embedding
+              table + learned positions, LayerNorm, two `bert` layers whose attention masks the
+              request's own padding, Where(Unsqueeze(Equal(ids, 0)), -inf, scores), CLS-token head.
+* `bert_ids_hf` the same at 160 tokens (two query blocks, five key tiles) and 4 heads of 32, with a
+              token-type row, a per-head relative-position table and the HF extended attention mask
+              Add(scores, (1 - Cast(Greater(ids, 0))) * -10000): table and key mask together.
+`synthetic_input(model, batch)` gives inputs of the right shape (token-id models: float32 ids in
+[1, V), sample i padded with 0 past a length that cycles through 1, 32, S, 45, 33, every third sample
+with one interior pad id).  The CPU executor is the fp32
 oracle for all of them (tests/test_gpu_general.py).
 """
 from __future__ import annotations
@@ -68,9 +76,12 @@ SPECS = {
     "bert_relpos": dict(seq=40, dim=128, heads=4, ffn=256, layers=2, classes=3),
     "bert_window": dict(seq=72, dim=128, heads=2, ffn=256, layers=2, classes=3, window=8),
     "bert_keymask": dict(seq=40, dim=128, heads=2, ffn=256, layers=2, classes=3, masked_keys=9),
+    "bert_ids": dict(seq=48, dim=128, heads=2, ffn=256, layers=2, classes=3, vocab=1000, pad=0),
+    "bert_ids_hf": dict(seq=160, dim=128, heads=4, ffn=256, layers=2, classes=3, vocab=1000, pad=0),
 }
 
 MASKED = ("gpt_causal", "bert_relpos", "bert_window", "bert_keymask")
+TOKEN_IDS = ("bert_ids", "bert_ids_hf")
 
 
 def _rng(seed):
@@ -273,6 +284,92 @@ def build_masked_encoder(seed: int = 0, opset: int = 17, spec: str = "bert_relpo
     w = g.init("classifier.weight", _lin(rng, D, (s["classes"], D)))
     b = g.init("classifier.bias", (0.1 * rng.standard_normal(s["classes"])).astype(np.float32))
     y = g.node("Gemm", [pooled, w, b], name="classifier", transB=1)
+    g.output(y, ["N", s["classes"]])
+    return g.model_proto(opset=opset), dict(g.initializers)
+
+
+def build_token_encoder(seed: int = 0, opset: int = 17, spec: str = "bert_ids",
+                        int_input: bool = False) -> Tuple[bytes, Dict[str, np.ndarray]]:
+    """Token-id encoders (`bert_ids`, `bert_ids_hf`): the graph input is [N, S] token ids carried as
+    numbers (declared FLOAT, or INT64 with int_input), embedded by a Gather, and the attention mask
+    is computed from the ids themselves (pad id 0).  Returns (model bytes, initializers)."""
+    from ..utils.onnx_writer import INT64
+
+    s = SPECS[spec]
+    rng = _rng(seed)
+    S, D, H, F, V = s["seq"], s["dim"], s["heads"], s["ffn"], s["vocab"]
+    hd = D // H
+    hf = spec == "bert_ids_hf"
+    g = GraphBuilder(name=spec)
+    x = g.input("input_ids", ["N", S], elem_type=INT64) if int_input else g.input("input_ids", ["N", S])
+    ids = x if int_input else g.node("Cast", [x], name="ids_int", to=INT64)
+    table = g.init("embeddings.word", (0.5 * rng.standard_normal((V, D))).astype(np.float32))
+    h = g.node("Gather", [table, ids], name="embeddings.lookup", axis=0)
+    h = g.node("Add", [h, g.init("embeddings.position", (0.5 * rng.standard_normal((1, S, D))).astype(np.float32))],
+               name="embeddings.add_position")
+    if hf:
+        h = g.node("Add", [h, g.init("embeddings.token_type", (0.5 * rng.standard_normal(D)).astype(np.float32))],
+                   name="embeddings.add_type")
+    heads_shape = g.const(np.array([0, 0, H, hd], np.int64), "heads_shape")
+    merge_shape = g.const(np.array([0, 0, D], np.int64), "merge_shape")
+    sqrt2 = g.const(np.array(1.4142135381698608, np.float32), "sqrt2")
+    one = g.const(np.array(1.0, np.float32), "one")
+    half = g.const(np.array(0.5, np.float32), "half")
+    axes12 = g.const(np.array([1, 2], np.int64), "mask_axes")
+    if hf:  # HF: extended = (1 - mask[:, None, None, :]) * -10000, mask = ids > 0, from the float input
+        m = g.node("Cast", [g.node("Greater", [x, g.const(np.array(0, np.int64 if int_input else np.float32), "pad_id")],
+                                   name="attention_mask")], name="attention_mask_f", to=1)
+        m = g.node("Unsqueeze", [m, axes12], name="extended_mask")
+        key_term = g.node("Mul", [g.node("Sub", [one, m], name="inverted_mask"),
+                                  g.const(np.array(-10000.0, np.float32), "mask_value")], name="additive_mask")
+    else:  # hidden = ids == pad on the integer ids
+        hidden = g.node("Unsqueeze", [g.node("Equal", [ids, g.const(np.array(s["pad"], np.int64), "pad_id")],
+                                             name="is_pad"), axes12], name="pad_mask")
+        fill = g.const(np.array(-np.inf, np.float32), "mask_fill")
+
+    def linear(inp, name, fin, fout):
+        w = g.init(name + ".weight", _lin(rng, fin, (fin, fout)))
+        b = g.init(name + ".bias", (0.02 * rng.standard_normal(fout)).astype(np.float32))
+        return g.node("Add", [g.node("MatMul", [inp, w], name=name + "/MatMul"), b], name=name + "/Add")
+
+    def ln(inp, name):
+        gw = g.init(name + ".weight", (1.0 + 0.1 * rng.standard_normal(D)).astype(np.float32))
+        gb = g.init(name + ".bias", (0.1 * rng.standard_normal(D)).astype(np.float32))
+        return g.node("LayerNormalization", [inp, gw, gb], name=name, axis=-1, epsilon=1e-5)
+
+    h = ln(h, "embeddings.ln")
+    for i in range(s["layers"]):
+        p = "layer%d." % i
+        q = linear(h, p + "query", D, D)
+        k = linear(h, p + "key", D, D)
+        v = linear(h, p + "value", D, D)
+        q = g.node("Transpose", [g.node("Reshape", [q, heads_shape], name=p + "q_heads")], name=p + "q_perm",
+                   perm=[0, 2, 1, 3])
+        k = g.node("Transpose", [g.node("Reshape", [k, heads_shape], name=p + "k_heads")], name=p + "k_perm",
+                   perm=[0, 2, 3, 1])
+        v = g.node("Transpose", [g.node("Reshape", [v, heads_shape], name=p + "v_heads")], name=p + "v_perm",
+                   perm=[0, 2, 1, 3])
+        sc = g.node("Div", [g.node("MatMul", [q, k], name=p + "scores"),
+                            g.const(np.array(math.sqrt(hd), np.float32), "sqrt_d")], name=p + "scale")
+        if hf:
+            rel = g.init(p + "rel_bias", rng.standard_normal((1, H, S, S)).astype(np.float32))
+            sc = g.node("Add", [g.node("Add", [sc, rel], name=p + "rel_bias/Add"), key_term], name=p + "mask/Add")
+        else:
+            sc = g.node("Where", [hidden, fill, sc], name=p + "mask")
+        sc = g.node("Softmax", [sc], name=p + "softmax", axis=-1)
+        c = g.node("MatMul", [sc, v], name=p + "context")
+        c = g.node("Reshape", [g.node("Transpose", [c], name=p + "ctx_perm", perm=[0, 2, 1, 3]), merge_shape],
+                   name=p + "ctx_merge")
+        h = ln(g.node("Add", [linear(c, p + "attn_out", D, D), h], name=p + "residual1"), p + "ln1")
+        m1 = linear(h, p + "intermediate", D, F)
+        t = g.node("Div", [m1, sqrt2], name=p + "gelu/div")
+        t = g.node("Add", [g.node("Erf", [t], name=p + "gelu/erf"), one], name=p + "gelu/add")
+        t = g.node("Mul", [g.node("Mul", [m1, t], name=p + "gelu/mul"), half], name=p + "gelu/half")
+        h = ln(g.node("Add", [linear(t, p + "output", F, D), h], name=p + "residual2"), p + "ln2")
+    cls = g.node("Gather", [h, g.const(np.array(0, np.int64), "cls_index")], name="cls_token", axis=1)
+    w = g.init("classifier.weight", _lin(rng, D, (s["classes"], D)))
+    b = g.init("classifier.bias", (0.1 * rng.standard_normal(s["classes"])).astype(np.float32))
+    y = g.node("Gemm", [cls, w, b], name="classifier", transB=1)
     g.output(y, ["N", s["classes"]])
     return g.model_proto(opset=opset), dict(g.initializers)
 
@@ -520,7 +617,9 @@ BUILDERS = {"mlp": build_mlp, "bert": build_bert, "se_cnn": build_se_cnn, "ratio
             "gpt_causal": lambda seed=0: build_masked_encoder(seed, spec="gpt_causal"),
             "bert_relpos": lambda seed=0: build_masked_encoder(seed, spec="bert_relpos"),
             "bert_window": lambda seed=0: build_masked_encoder(seed, spec="bert_window"),
-            "bert_keymask": lambda seed=0: build_masked_encoder(seed, spec="bert_keymask")}
+            "bert_keymask": lambda seed=0: build_masked_encoder(seed, spec="bert_keymask"),
+            "bert_ids": lambda seed=0: build_token_encoder(seed, spec="bert_ids"),
+            "bert_ids_hf": lambda seed=0: build_token_encoder(seed, spec="bert_ids_hf")}
 
 
 def build_onnx(name: str, seed: int = 0) -> bytes:
@@ -533,9 +632,35 @@ def input_shape(name: str):
         return (s["in_features"],)
     if name in ("bert", "bert_long", "bert_hd32", "bert_hd128", "token_mixer", "ln_wide", "ln_offset") + MASKED:
         return (s["seq"] * s["dim"],)
+    if name in TOKEN_IDS:
+        return (s["seq"],)
     return (s["in_ch"], s["image"], s["image"])
 
 
 def synthetic_input(name: str, batch: int, seed: int = 1) -> np.ndarray:
     rng = np.random.default_rng(seed)
+    if name in TOKEN_IDS:
+        return synthetic_ids(name, batch, rng)
     return rng.standard_normal((batch,) + input_shape(name)).astype(np.float32)
+
+
+def synthetic_lengths(name: str, batch: int):
+    """Sequence length of each sample of a token-id batch: a first-tile length, a tile edge, the full
+    length and two mid-tile lengths, in turn."""
+    S = SPECS[name]["seq"]
+    return [min(S, (1, 32, S, 45, 33)[i % 5]) for i in range(batch)]
+
+
+def synthetic_ids(name: str, batch: int, rng, full_length: bool = False) -> np.ndarray:
+    """float32 ids in [1, V); past its length a row holds the pad id; every third sample has one
+    pad id inside its length (a hole)."""
+    s = SPECS[name]
+    S, V, pad = s["seq"], s["vocab"], s["pad"]
+    ids = rng.integers(1, V, size=(batch, S)).astype(np.float32)
+    if full_length:
+        return ids
+    for i, n in enumerate(synthetic_lengths(name, batch)):
+        ids[i, n:] = pad
+        if i % 3 == 2 and n >= 3:
+            ids[i, n // 2] = pad
+    return ids

@@ -726,6 +726,12 @@ def _sig_kernels():
     L.die_kern_attention.argtypes = [u64] * 4 + [i] * 8 + [C.c_float, u64, i]
     L.die_kern_attention_masked.restype = i
     L.die_kern_attention_masked.argtypes = [u64] * 4 + [i] * 8 + [C.c_float, u64, i, u64, i, i, i]
+    L.die_kern_attention_keymask.restype = i
+    L.die_kern_attention_keymask.argtypes = [u64] * 4 + [i] * 8 + [C.c_float, u64, i, u64, i, i, i, u64, u64]
+    L.die_kern_embed_tokens.restype = i
+    L.die_kern_embed_tokens.argtypes = [u64, u64, i, u64, u64, u64, i, i, i, i, u64, i, u64, u64, i, i, C.c_float, i, i]
+    L.die_token_index.restype = i
+    L.die_token_index.argtypes = [C.c_float, i]
     L.die_kern_set_attention_variant.restype = None
     L.die_kern_set_attention_variant.argtypes = [i]
     L.die_kern_set_decode_variant.restype = None

@@ -347,6 +347,77 @@ def gather_rows(x, idx, split=False):
     return _out(y, split)
 
 
+_PAD_OPS = {"eq": 0, "gt": 1, "lt": 2}
+
+
+def embed_tokens(ids, table, pos=None, type_row=None, pad_test=None, split=False):
+    """Embedding lookup on token ids carried as numbers: ids [B, S] (any float / int dtype; the kernel
+    reads them as fp32), table [V, D] fp32, pos [S, D], type_row [D] ->
+    rows[b, s] = table[idx(ids[b, s])] + pos[s] + type_row summed in fp32, with idx = truncate and
+    clamp to [0, V - 1] (NaN -> 0).  rows: [B, S, Dp] bf16 (split: fp32 from the hi / lo planes), Dp = D
+    rounded up to 8, the pad columns 0.
+    pad_test: None, a pad id, or (op, value) with op in "eq" / "gt" / "lt": a key is PADDING where
+    `id op value` holds.  Then also returns the attention key data: kvis [B, Sp] fp32 (0 visible,
+    -inf padding and columns >= S; Sp = S rounded up to 32) and kend [B] int32 = 1 + the last
+    visible key (0: none); else (rows, None, None).
+    A table whose rows are 16-byte aligned with a pitch that is a multiple of 4 and >= Dp is read in
+    place (a row slice of a larger table, say); any other is copied to pitch Dp."""
+    import torch
+
+    B, S = ids.shape
+    V, D = table.shape
+    Dp = (D + 7) // 8 * 8
+    dev = table.device
+    idf = ids.to(device=dev, dtype=torch.float32).contiguous()
+
+    def padded(t, rows):
+        if t is None:
+            return None
+        t = t.to(device=dev, dtype=torch.float32).reshape(rows, D)
+        if Dp == D:
+            return t.contiguous()
+        o = torch.zeros((rows, Dp), dtype=torch.float32, device=dev)
+        o[:, :D] = t
+        return o
+
+    if (table.dtype == torch.float32 and table.dim() == 2 and table.stride(1) == 1 and table.stride(0) >= Dp
+            and table.stride(0) % 4 == 0 and table.data_ptr() % 16 == 0):
+        tab, ldt = table, int(table.stride(0))
+    else:
+        tab, ldt = padded(table, V), Dp
+    ps, ty = padded(pos, S), padded(type_row, 1)
+    out = torch.empty(((2,) if split else ()) + (B, S, Dp), dtype=torch.bfloat16, device=dev)
+    kvis = kend = None
+    Sp = op = neg = 0
+    val = 0.0
+    if pad_test is not None:
+        name, val = pad_test if isinstance(pad_test, (tuple, list)) else ("eq", pad_test)
+        op, neg = _PAD_OPS[name], 1  # visible = not (id op value)
+        Sp = (S + 31) // 32 * 32
+        kvis = torch.empty((B, Sp), dtype=torch.float32, device=dev)
+        kend = torch.empty((B,), dtype=torch.int32, device=dev)
+    rc = native.kernels().die_kern_embed_tokens(_ptr(idf), _ptr(tab), ldt, _ptr(ps), _ptr(ty), _ptr(out), B, S, V, Dp,
+                                                _stream(), int(split), _ptr(kvis), _ptr(kend), Sp, op, float(val), neg, 0)
+    _check(rc, "embed_tokens")
+    return _out(out, split), kvis, kend
+
+
+def key_mask_data(visible):
+    """bool [B, S] (True = visible key) -> the attention kernels' key data (kvis [B, Sp] fp32 with 0 /
+    -inf and -inf in the columns >= S, kend [B] int32 = 1 + the last visible key), as embed_tokens()
+    writes it."""
+    import torch
+
+    B, S = visible.shape
+    Sp = (S + 31) // 32 * 32
+    vis = visible.bool()
+    kvis = torch.full((B, Sp), float("-inf"), dtype=torch.float32, device=vis.device)
+    kvis[:, :S] = torch.where(vis, 0.0, float("-inf"))
+    pos = torch.arange(1, S + 1, device=vis.device, dtype=torch.int32)
+    kend = (vis.to(torch.int32) * pos).amax(dim=1).to(torch.int32).contiguous()
+    return kvis, kend
+
+
 _LOG2E = 1.4426950408889634
 
 
@@ -366,8 +437,19 @@ def _attention_bias(bias, S, heads):
     return table, int(bias.shape[0]), Sp
 
 
-def _attention_launch(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, split, bias, causal, what):
-    if bias is None and not causal:  # the unmasked entry point, as before
+def _attention_launch(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, split, bias, causal, what, key_mask=None):
+    if key_mask is not None:
+        if not isinstance(key_mask, (tuple, list)) and tuple(key_mask.shape) != (B, S):
+            raise ValueError("key mask must be bool [B, S] = [%d, %d], got %s" % (B, S, tuple(key_mask.shape)))
+        kvis, kend = key_mask if isinstance(key_mask, (tuple, list)) else key_mask_data(key_mask)
+        Sp = (S + 31) // 32 * 32
+        if tuple(kvis.shape) != (B, Sp) or tuple(kend.shape) != (B,):
+            raise ValueError("key mask must be bool [B, S] or (kvis [B, Sp] fp32, kend [B] int32), B = %d, S = %d" % (B, S))
+        table, hb, _ = _attention_bias(bias, S, heads) if bias is not None else (None, 0, 0)
+        rc = native.kernels().die_kern_attention_keymask(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, _stream(),
+                                                         split, _ptr(table), hb, Sp, int(bool(causal)), _ptr(kvis),
+                                                         _ptr(kend))
+    elif bias is None and not causal:  # the unmasked entry point, as before
         rc = native.kernels().die_kern_attention(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, _stream(), split)
     else:
         table, hb, Sp = _attention_bias(bias, S, heads) if bias is not None else (None, 0, 0)
@@ -376,12 +458,15 @@ def _attention_launch(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, spli
     _check(rc, what)
 
 
-def attention(q, k, v, heads, scale=None, bias=None, causal=False):
+def attention(q, k, v, heads, scale=None, bias=None, causal=False, key_mask=None):
     """q/k/v: [B, S, H*D] bf16 (may be column slices of a wider tensor, row stride = stride(1)).
     Returns softmax(scale * Q K^T + bias) V merged back to [B, S, H*D] bf16.
     bias: fp32 [S, S] (shared by the heads) or [H, S, S], natural units, -inf = masked, the same for
     every image of the batch; causal: key j is visible to query i iff j <= i (on top of any bias).
-    A query row with no visible key at all is undefined (NaN in ONNX): the caller must not pass one."""
+    A query row with no visible key at all is undefined (NaN in ONNX): the caller must not pass one.
+    key_mask: per-sample padding, bool [B, S] with True = visible key, or the (kvis, kend) pair of
+    embed_tokens() / key_mask_data(); combines with a bias, not with causal (an error).  A sample
+    without any visible key gets all-zero rows."""
     import torch
 
     B, S, C = q.shape
@@ -391,7 +476,7 @@ def attention(q, k, v, heads, scale=None, bias=None, causal=False):
     out = torch.empty((B, S, C), dtype=torch.bfloat16, device=q.device)
     sc = float(scale if scale is not None else 1.0 / np.sqrt(D))
     _attention_launch(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, S, heads, D, q.stride(1), k.stride(1), v.stride(1), C,
-                      sc, 0, bias, causal, "attention")
+                      sc, 0, bias, causal, "attention", key_mask)
     return out
 
 
@@ -401,10 +486,10 @@ def set_attention_variant(v):
     native.kernels().die_kern_set_attention_variant(int(v))
 
 
-def attention_qkv_split(qkv, heads, scale=None, bias=None, causal=False):
+def attention_qkv_split(qkv, heads, scale=None, bias=None, causal=False, key_mask=None):
     """fp32 mode: qkv [B, S, 3*C] float (Q | K | V columns) -> fp32 [B, S, C] through the split kernel
     (planes of the packed QKV rows, like the engine's fused QKV GEMM output).  bias / causal: as
-    attention() takes them (the bias is fp32 in both precisions)."""
+    attention() takes them (the bias is fp32 in both precisions); key_mask: likewise."""
     import torch
 
     B, S, C3 = qkv.shape
@@ -415,7 +500,7 @@ def attention_qkv_split(qkv, heads, scale=None, bias=None, causal=False):
     sc = float(scale if scale is not None else 1.0 / np.sqrt(D))
     base = _ptr(planes)
     _attention_launch(base, base + 2 * C, base + 4 * C, _ptr(out), B, S, heads, D, C3, C3, C3, C, sc, 1, bias, causal,
-                      "attention (split)")
+                      "attention (split)", key_mask)
     return join_planes(out)
 
 

@@ -11,9 +11,17 @@ default variant (bitwise) and against torch float64.
   bias_heads  a per-head [H, S, S] table
   causal      the causal flag (no table); at long S compare its time to `none`: a block fetches
               only the key tiles up to its last query and a wave skips the tiles past its own
+  keypad      the per-sample key (padding) mask: sample i sees the first ceil(fill_i * S) keys, its
+              key data (kvis, kend) as embed_tokens writes it; a block walks only the key tiles
+              below kend[i], so compare its time to `none` and to `keypad_table`
+  keypad_table  the same mask through the BIAS mode, as a shared [1, S, S] table (the first fill
+              value for every sample: one table serves the whole batch)
+--fill (repeatable) gives the visible fraction per sample of the keypad modes, a comma-separated
+list cycled over the batch; each --fill is one measured case (default: 1.0).
 The masked modes run the default variant only (they have no two-tiles-ahead instantiation).
 
-  python tools/attn_bench.py [--batch 32] [--seq 197] [--mask none,bias,bias_heads,causal] [--md out.md]
+  python tools/attn_bench.py [--batch 32] [--seq 197] [--mask none,bias,bias_heads,causal,keypad,keypad_table]
+                             [--fill 1.0 --fill 0.5 --fill 1.0,0.5,0.25] [--md out.md]
 """
 import argparse
 import os
@@ -22,7 +30,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-MASKS = ("none", "bias", "bias_heads", "causal")
+MASKS = ("none", "bias", "bias_heads", "causal", "keypad", "keypad_table")
 
 
 def main():
@@ -31,8 +39,11 @@ def main():
     ap.add_argument("--seq", type=int, default=197)
     ap.add_argument("--heads", type=int, default=12)
     ap.add_argument("--mask", default="none", help="comma-separated: " + ", ".join(MASKS))
+    ap.add_argument("--fill", action="append", default=None,
+                    help="keypad modes: visible fraction per sample, comma-separated, cycled; repeatable")
     ap.add_argument("--md", default="")
     a = ap.parse_args()
+    fills = [[float(f) for f in spec.split(",") if f] for spec in (a.fill or ["1.0"])]
     masks = [m for m in a.mask.split(",") if m]
     for m in masks:
         if m not in MASKS:
@@ -54,7 +65,18 @@ def main():
     L = native.kernels()
     lines = ["# Streaming attention, B=%d S=%d H=%d D=64 (MI355X)" % (B, S, H), "",
              "| mode | mask | variant | us | rel err vs fp64 | bitwise = variant 0 |", "|---|---|---:|---:|---:|---|"]
-    for mask in masks:
+    cases = []
+    for m in masks:
+        cases += [(m, f) for f in fills] if m.startswith("keypad") else [(m, None)]
+    for mask, fill in cases:
+        label = mask
+        kvis = kend = None
+        if fill is not None:
+            if mask == "keypad_table":
+                fill = fill[:1]
+            label = "%s fill %s" % (mask, ",".join("%g" % f for f in fill))
+            n_vis = torch.tensor([max(1, min(S, int(np.ceil(fill[i % len(fill)] * S)))) for i in range(B)], device="cuda")
+            visible = torch.arange(S, device="cuda")[None, :] < n_vis[:, None]  # [B, S]
         # the additive term of the float64 reference and the kernel's table ([Hb][S][Sp], exp2 units)
         bias_nat = None
         if mask == "bias":
@@ -65,6 +87,12 @@ def main():
         if mask == "causal":
             i = torch.arange(S, device="cuda")
             term = torch.where(i[None, :] <= i[:, None], 0.0, -float("inf")).double()
+        if mask == "keypad":
+            kvis, kend = K.key_mask_data(visible)
+            term = torch.where(visible, 0.0, -float("inf")).double()[:, None, None, :]
+        if mask == "keypad_table":
+            bias_nat = torch.where(visible[0], 0.0, -float("inf"))[None, None, :].expand(1, S, S).contiguous()
+            term = bias_nat.double()
         ref = (torch.softmax(scores + term, -1) @ v).transpose(1, 2).reshape(B, S, C)
         table, hb = None, 0
         if bias_nat is not None:
@@ -82,7 +110,11 @@ def main():
 
             def launch():
                 st = torch.cuda.current_stream().cuda_stream
-                if mask == "none":
+                if mask == "keypad":
+                    rc = L.die_kern_attention_keymask(base, base + 2 * C, base + 4 * C, out.data_ptr(), B, S, H, D,
+                                                      3 * C, 3 * C, 3 * C, C, float(1 / np.sqrt(D)), st, int(split), 0, 0,
+                                                      Sp, 0, kvis.data_ptr(), kend.data_ptr())
+                elif mask == "none":
                     rc = L.die_kern_attention(base, base + 2 * C, base + 4 * C, out.data_ptr(), B, S, H, D, 3 * C,
                                               3 * C, 3 * C, C, float(1 / np.sqrt(D)), st, int(split))
                 else:
@@ -116,7 +148,7 @@ def main():
                     e1.record()
                     e1.synchronize()
                     ts.append(e0.elapsed_time(e1) * 1000 / 20)
-                lines.append("| %s | %s | %d | %.2f | %.1e | %s |" % ("fp32 split" if split else "bf16", mask, var,
+                lines.append("| %s | %s | %d | %.2f | %.1e | %s |" % ("fp32 split" if split else "bf16", label, var,
                                                                        statistics.median(ts), err, same))
                 print(lines[-1], flush=True)
             K.set_attention_variant(0)

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Per-op device time of one forward on the HIP engine (events around eager launches of the tuned
-kernels), written as a markdown table + JSON.  Usage: op_profile.py --arch resnet50|vit_b16 --batch 32"""
+kernels), written as a markdown table + JSON.  Usage: op_profile.py --arch resnet50|vit_b16 --batch 32
+Token-id models (--arch bert_ids|bert_ids_hf) are profiled on a batch of ids fed first: --ids full
+(every sequence full length) or synthetic (models/generic.py synthetic lengths and holes)."""
 import argparse
 import json
 import os
@@ -12,7 +14,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=["resnet50", "vit_b16"], default="resnet50")
+    ap.add_argument("--arch", choices=["resnet50", "vit_b16", "bert_ids", "bert_ids_hf"], default="resnet50")
+    ap.add_argument("--ids", choices=["full", "synthetic"], default="full", help="token-id models: the profiled batch")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--out", default="")
@@ -38,7 +41,12 @@ def main():
     import die_amd  # noqa: F401
     from die_amd import native
 
-    if a.arch == "vit_b16":
+    token_ids = a.arch.startswith("bert_ids")
+    if token_ids:
+        from die_amd.models import generic as m
+
+        cfg = None
+    elif a.arch == "vit_b16":
         from die_amd.models import vit as m
 
         cfg = m.ViTConfig()
@@ -48,7 +56,7 @@ def main():
         cfg = m.ResNetConfig()
     d = tempfile.mkdtemp()
     path = os.path.join(d, a.arch + ".onnx")
-    open(path, "wb").write(m.build_onnx(cfg)[0])
+    open(path, "wb").write(m.build_onnx(a.arch) if token_ids else m.build_onnx(cfg)[0])
     native.kernels().die_kern_set_layernorm_xcd(int(a.ln_xcd))
     e = native.Engine(path, device="hip", max_batch=a.batch, precision=a.precision,
                       tune_warm_input=a.tune_warm_input, fuse_pairs=not a.no_fuse_pairs,
@@ -56,11 +64,17 @@ def main():
                       fuse_stem_pool=not a.no_fuse_stem_pool, fuse_gap_fc=a.fuse_gap_fc, fold_layernorm=not a.no_fold_layernorm,
                       ln_stats_epilogue=not a.no_ln_stats_epilogue, tune_in_graph=a.tune_in_graph, conv_order=a.conv_order,
                       tune_orders=not a.no_tune_orders, tune_tail=a.tune_tail,
+                      **({"pipeline_depth": 1} if token_ids else {}),
                       **({} if a.tune_streamk < 0 else {"tune_streamk": bool(a.tune_streamk)}))
+    if token_ids:  # one pipeline slot: the profiled forwards read the ids this run leaves in it
+        import numpy as np
+
+        e.run(m.synthetic_ids(a.arch, a.batch, np.random.default_rng(1), full_length=a.ids == "full"))
     p = e.profile(a.batch, a.iters)
     info = e.refresh_info()
     e.close()
-    lines = ["# %s per-op device time, batch %d (MI355X, %s, tuned kernels)" % (a.arch, p["batch"], a.precision), "",
+    lines = ["# %s per-op device time, batch %d (MI355X, %s, tuned kernels%s)" % (
+                 a.arch, p["batch"], a.precision, ", %s ids" % a.ids if token_ids else ""), "",
              "Total %.1f us per forward = %.1f TFLOP/s over the whole graph; %.0f images/s device-bound." % (
                  p["total_us"], p["tflops"], p["batch"] / p["total_us"] * 1e6), "",
              "In-graph retune: %s (%s candidates timed in place, %s convs changed)." % (
