@@ -205,6 +205,17 @@ int die_kern_embed_tokens(uint64_t ids, uint64_t table, int ldt, uint64_t pos, u
                                              P<float>(kvis), P<int>(kend), Sp, pad_op, pad_c, pad_neg, pad_trunc));
 }
 
+// Token pooling + L2 normalisation (kernels.h pool_tokens); kvis / kend 0 = unmasked, ws / counters 0 = none
+int die_kern_pool_tokens(uint64_t x, uint64_t out, uint64_t out_f32, int B, int Sq, int C, int D, uint64_t kvis,
+                         uint64_t kend, int Sp, float clip_min, int normalize, float eps, uint64_t stream, uint64_t live,
+                         int split, uint64_t ws, uint64_t ws_bytes, uint64_t counters, int counters_n) {
+  return static_cast<int>(kern::pool_tokens(P<const uint16_t>(x), P<uint16_t>(out), P<float>(out_f32), B, Sq, C, D,
+                                            P<const float>(kvis), P<const int>(kend), Sp, clip_min, normalize, eps,
+                                            S(stream), P<const long long>(live), split, P<float>(ws),
+                                            static_cast<size_t>(ws_bytes), P<int>(counters), counters_n));
+}
+uint64_t die_kern_pool_tokens_ws_bytes(int B, int C) { return kern::pool_tokens_ws_bytes(B, C); }
+
 // the kernels' id -> table row rule on the host (k::token_index)
 int die_token_index(float x, int V) { return kern::token_index_host(x, V); }
 
@@ -367,8 +378,8 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
       static const char* kinds[] = {"input_prep", "conv", "pool", "gap", "affine", "to_nchw_f32", "bf16_to_f32",
                                     "layernorm", "tokens", "gather_rows", "attention", "stem", "gconv", "softmax",
                                     "rows_prep", "copy_cols", "binary", "unary", "conv_pair", "pad", "where", "resize", "bmm", "gap_fc",
-                                    "embed_tokens"};
-      static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::EMBED_TOKENS + 1, "one name per PlanOp kind");
+                                    "embed_tokens", "pool_tokens"};
+      static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::POOL_TOKENS + 1, "one name per PlanOp kind");
       e["kind"] = kinds[o.kind];
       e["name"] = o.name;
       e["gflop"] = o.flops_per_sample / 1e9;
@@ -434,6 +445,14 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
           e["pad_negated"] = o.is_max != 0;
           e["pad_truncated"] = o.in_relu != 0;
         }
+      }
+      if (o.kind == PlanOp::POOL_TOKENS) {
+        e["masked"] = o.key_mask != 0;  // mean over the visible tokens (key data from the embed_tokens op)
+        e["normalize"] = o.act != 0;
+        e["clip_min"] = static_cast<double>(o.clip_lo);
+        e["eps"] = static_cast<double>(o.eps);
+        e["seq"] = o.S;
+        e["dim"] = o.Cp;
       }
       if (o.kind == PlanOp::LAYERNORM) e["stats_only"] = o.stats_only != 0;
       if (o.kind == PlanOp::CONV || o.kind == PlanOp::TOKENS) e["stats_out"] = o.out_stats >= 0;  // writes the partials

@@ -642,7 +642,10 @@ CpuValuePtr op_reduce(const Node& n, const std::vector<const CpuValue*>& in, int
     }
   }
   auto y = make_f(os);
-  const bool is_max = n.op_type == "ReduceMax";
+  const bool is_max = n.op_type == "ReduceMax", is_l2 = n.op_type == "ReduceL2";
+  std::vector<float> as_f;  // a mask summed without a Cast
+  if (x.is_int) as_f.assign(x.i.begin(), x.i.end());
+  const float* xf = x.is_int ? as_f.data() : x.f.data();
   std::vector<double> acc(static_cast<size_t>(y->numel()), is_max ? -std::numeric_limits<double>::infinity() : 0.0);
   auto xs = strides_of(x.shape), kst = strides_of(ks);
   const int64_t total = x.numel();
@@ -656,11 +659,34 @@ CpuValuePtr op_reduce(const Node& n, const std::vector<const CpuValue*>& in, int
       rem %= xs[k];
       if (!red[k]) o += idx * kst[k];
     }
-    if (is_max) acc[o] = std::max(acc[o], static_cast<double>(x.f[e]));
-    else acc[o] += x.f[e];
+    if (is_max) acc[o] = std::max(acc[o], static_cast<double>(xf[e]));
+    else if (is_l2) acc[o] += static_cast<double>(xf[e]) * xf[e];
+    else acc[o] += xf[e];
   }
   const bool mean = n.op_type == "ReduceMean";
-  for (size_t k = 0; k < acc.size(); ++k) y->f[k] = static_cast<float>(mean ? acc[k] / cnt : acc[k]);
+  for (size_t k = 0; k < acc.size(); ++k)
+    y->f[k] = static_cast<float>(mean ? acc[k] / cnt : is_l2 ? std::sqrt(acc[k]) : acc[k]);
+  return y;
+}
+
+// LpNormalization (p = 1 or 2, any axis): x / ||x||_p along the axis.  ONNX has no epsilon here: an
+// all-zero slice gives 0 / 0 = NaN.
+CpuValuePtr op_lp_normalization(const Node& n, const CpuValue& x) {
+  const int64_t p = n.get_int("p", 2);
+  if (p != 1 && p != 2) fail(n, "p must be 1 or 2");
+  const int64_t axis = norm_axis(n.get_int("axis", -1), x.shape.size());
+  int64_t inner = 1;
+  for (size_t k = static_cast<size_t>(axis) + 1; k < x.shape.size(); ++k) inner *= x.shape[k];
+  const int64_t len = x.shape[axis], outer = len * inner != 0 ? x.numel() / (len * inner) : 0;
+  auto y = make_f(x.shape);
+  for (int64_t o = 0; o < outer; ++o)
+    for (int64_t i = 0; i < inner; ++i) {
+      const float* src = x.f.data() + o * len * inner + i;
+      double acc = 0.0;
+      for (int64_t k = 0; k < len; ++k) acc += p == 1 ? std::fabs(static_cast<double>(src[k * inner])) : static_cast<double>(src[k * inner]) * src[k * inner];
+      const float nrm = static_cast<float>(p == 1 ? acc : std::sqrt(acc));
+      for (int64_t k = 0; k < len; ++k) y->f[o * len * inner + i + k * inner] = src[k * inner] / nrm;
+    }
   return y;
 }
 
@@ -1108,8 +1134,11 @@ CpuValuePtr CpuExecutor::run(const CpuValuePtr& input, std::unordered_map<std::s
       out = op_softmax(n, *in[0], opset);
     } else if (op == "LayerNormalization") {
       out = op_layernorm(n, *in[0], in.size() > 1 ? in[1] : nullptr, in.size() > 2 ? in[2] : nullptr);
-    } else if (op == "ReduceMean" || op == "ReduceSum" || op == "ReduceMax") {
+    } else if (op == "ReduceMean" || op == "ReduceSum" || op == "ReduceMax" || op == "ReduceL2") {
       out = op_reduce(n, in, opset);
+    } else if (op == "LpNormalization") {
+      if (in[0]->is_int) fail(n, "needs a float input");
+      out = op_lp_normalization(n, *in[0]);
     } else if (op == "Pad") {
       out = op_pad(n, in);
     } else if (op == "ConvTranspose") {

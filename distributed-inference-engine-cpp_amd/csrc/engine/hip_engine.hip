@@ -1514,6 +1514,16 @@ class HipEngine : public Engine {
                                  static_cast<float*>(buf(op.out2)), static_cast<int*>(buf(op.out3)),
                                  op.out2 >= 0 ? (op.S + 31) / 32 * 32 : 0, op.act, op.clip_lo, op.is_max, op.in_relu);
           break;
+        case PlanOp::POOL_TOKENS:
+          e = kern::pool_tokens(static_cast<const uint16_t*>(buf(op.in)),
+                                op.out >= 0 ? static_cast<uint16_t*>(buf(op.out)) : nullptr,
+                                op.out_f32 != -1 ? static_cast<float*>(buf(op.out_f32)) : nullptr, B, op.S, op.C, op.Cp,
+                                op.key_mask ? static_cast<const float*>(buf(op.in4)) : nullptr,
+                                op.key_mask ? static_cast<const int*>(buf(op.in5)) : nullptr,
+                                op.key_mask ? (op.S + 31) / 32 * 32 : 0, op.clip_lo, op.act, op.eps, st, live, sp_,
+                                side ? ws_side_ : wss_[s % n_exec_], ws_bytes_, side ? counters_side_ : counterss_[s % n_exec_],
+                                kCounters);
+          break;
         case PlanOp::GCONV: {
           kern::GConvArgs g;
           g.x = static_cast<const uint16_t*>(buf(op.in));
@@ -1594,8 +1604,8 @@ class HipEngine : public Engine {
     static const char* kinds[] = {"input_prep", "conv", "pool", "gap", "affine", "to_nchw_f32", "bf16_to_f32",
                                   "layernorm", "tokens", "gather_rows", "attention", "stem", "gconv", "softmax",
                                   "rows_prep", "copy_cols", "binary", "unary", "conv_pair", "pad", "where", "resize", "bmm", "gap_fc",
-                                  "embed_tokens"};
-    static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::EMBED_TOKENS + 1, "one name per PlanOp kind");
+                                  "embed_tokens", "pool_tokens"};
+    static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::POOL_TOKENS + 1, "one name per PlanOp kind");
     Json out = Json::object();
     Json ops = Json::array();
     double total = 0;
@@ -1620,6 +1630,10 @@ class HipEngine : public Engine {
         o["bias_heads"] = op.bias_heads;
         o["causal"] = op.causal != 0;
         o["key_mask"] = op.key_mask != 0;
+      }
+      if (op.kind == PlanOp::POOL_TOKENS) {
+        o["masked"] = op.key_mask != 0;
+        o["normalize"] = op.act != 0;
       }
       total += us[i];
       ops.push_back(o);

@@ -54,6 +54,8 @@ struct Val {
     TOKCAT,      // Concat([cls, patch rows], axis=1)
     TOKEN_IDS,   // the rank-2 graph input [N, S] read as token ids (fp32 in the input buffer; H = S)
     KEYVIS,      // per-key boolean derived from the ids (padding): a pad test, a polarity, a shape
+    POOLV,       // masked mean pooling in progress (stage 0: rows x key mask [N, S, D], 1: their sum over the
+                 // tokens [N, D], 2: the count of visible tokens [N, D] / [N, 1]); buf / C / cl / H = the rows
     UNKNOWN      // produced by a node the planner could not lower (support report)
   } kind = NHWC;
   int C = 0, H = 1, W = 1;
@@ -82,6 +84,11 @@ struct Val {
   int kv_op = 0, kv_rank = 2;
   float kv_c = 0.f;
   bool kv_neg = false, kv_trunc = false, kv_add = false;
+  // KEYVIS for pooling: kv_last = unsqueezed at the LAST axis, [N, S, 1] (kv_rank 3), kv_D > 0 = then
+  // expanded to [N, S, kv_D].  POOLV keeps the mask's fields; pool_c = stage 2: the count's lower bound
+  bool kv_last = false;
+  int kv_D = 0;
+  float pool_c = 0.f;
   // SHAPE / BCAST_INIT / TOKCAT
   std::vector<int64_t> ints;
   bool known = true;
@@ -112,6 +119,8 @@ class Planner {
     for (size_t i = 0; i < m_.nodes.size(); ++i)
       for (auto& in : m_.nodes[i].inputs) consumers_[in].push_back(static_cast<int>(i));
     for (auto& o : m_.outputs) graph_outputs_.insert(o.name);
+    for (size_t i = 0; i < m_.nodes.size(); ++i)
+      for (auto& o : m_.nodes[i].outputs) producer_[o] = static_cast<int>(i);
     plan_.split = split_;
     define_graph_input();
 
@@ -323,6 +332,7 @@ class Planner {
     if (op == "Softmax") return lower_softmax(idx);
     if (op == "Clip") return lower_clip(idx);
     if (op == "ReduceMean") return lower_reduce_mean(idx);
+    if (op == "ReduceL2" || op == "LpNormalization") return lower_l2norm(idx);
     if (op == "ReduceSum" || op == "ReduceMax") {
       if (lower_spatial_reduce(idx, op == "ReduceSum" ? 1 : 2)) return;
       throw std::runtime_error(op + " " + n.name + ": only reductions over the spatial axes of an image or the token axis of rows");
@@ -980,7 +990,9 @@ class Planner {
   bool token_node(const Node& n) const {
     for (const auto& in : n.inputs) {
       auto it = vid_.find(in);
-      if (it != vid_.end() && (vals_[it->second].kind == Val::TOKEN_IDS || vals_[it->second].kind == Val::KEYVIS)) return true;
+      if (it != vid_.end() && (vals_[it->second].kind == Val::TOKEN_IDS || vals_[it->second].kind == Val::KEYVIS ||
+                               vals_[it->second].kind == Val::POOLV))
+        return true;
     }
     return false;
   }
@@ -999,6 +1011,7 @@ class Planner {
     const Node& n = m_.nodes[idx];
     const std::string& op = n.op_type;
     const std::string who = op + " " + n.name + ": ";
+    if (lower_pool_node(idx)) return;
     if (const Val* ids = n.inputs.empty() ? nullptr : val_if(n.in(0), Val::TOKEN_IDS)) {
       if (op == "Cast") {
         const int to = static_cast<int>(n.get_int("to", onnx::FLOAT));
@@ -1106,8 +1119,9 @@ class Planner {
       }
     throw std::runtime_error(who + "token ids feed only a Cast to INT64 / INT32, an embedding Gather (axis 0) and the pad "
                              "tests Equal / Greater / Less, and a key mask derived from them only Not, Cast, Unsqueeze / "
-                             "Reshape to [N, 1, 1, S], Sub(1, m), Mul(m, c <= -1e4) and the Where / Add on attention scores "
-                             "(masked mean pooling and other uses are out of scope)");
+                             "Reshape to [N, 1, 1, S], Sub(1, m), Mul(m, c <= -1e4), the Where / Add on attention scores and "
+                             "the masked mean over the tokens (Unsqueeze(-1), Expand to [N, S, D], Mul(rows, m), "
+                             "ReduceSum(m, axis 1)); other uses are out of scope");
   }
 
   // Gather(table [V, D] float initializer, ids, axis 0) [+ Add(positions [S, D] / [1, S, D])]
@@ -1177,6 +1191,15 @@ class Planner {
       throw std::runtime_error(who + "a key mask on attention scores must have the shape [N, 1, 1, S] (rank " +
                                std::to_string(m.kv_rank) + " here)");
     if (m.H != vals_[x.q].H) throw std::runtime_error(who + "the key mask's length is not the attention's");
+    bind_key_test(who, m, vis_when_true);
+    Val o = x;
+    o.kmask = true;
+    define(n.outputs[0], o);
+  }
+
+  // The model's one pad test, on the EMBED_TOKENS op that writes the key data (kvis, kend) for it:
+  // set by the first user (an attention or the token pooling), compared by every later one.
+  void bind_key_test(const std::string& who, const Val& m, bool vis_when_true) {
     if (key_op_ < 0)
       throw std::runtime_error(who + "a key mask needs the token embedding (EMBED_TOKENS writes the key data) lowered first");
     // visible = ((trunc ? trunc(id) : id) OP c) != neg
@@ -1196,9 +1219,328 @@ class Planner {
     } else if (e.act != m.kv_op || e.clip_lo != m.kv_c || e.is_max != neg || e.in_relu != (m.kv_trunc ? 1 : 0)) {
       throw std::runtime_error(who + "a second, different pad test (one key mask per model: every attention shares the key data)");
     }
-    Val o = x;
-    o.kmask = true;
-    define(n.outputs[0], o);
+  }
+
+  // ---- sentence embedders: masked mean over the tokens and L2 normalisation -------------------------
+  // vis [N, S] -> Unsqueeze(-1) [-> Expand to [N, S, D]] -> Cast = m;  Mul(rows, m) -> ReduceSum(axis 1)
+  // = the masked sum;  ReduceSum(m, axis 1) (or of the unexpanded [N, S] mask, keepdims 1)
+  // [-> Clip(min = c) / Max(., c)] = the count;  Div(sum, count) closes the pattern: one POOL_TOKENS op
+  // reading the key data of the plan's EMBED_TOKENS op.  An L2 normalisation that is the pooled
+  // vector's only reader sets the op's normalize flag; on any other rank-2 rows it is a POOL_TOKENS op
+  // with S = 1.
+  bool reduce_axes(const Node& n, std::vector<int64_t>& ax) const {
+    ax = n.get_ints("axes");
+    if (ax.empty() && n.inputs.size() > 1 && !n.in(1).empty()) return ints_of(n.in(1), ax) && !ax.empty();
+    return !ax.empty();
+  }
+
+  // `name` is written by ReduceSum(Mul(., .)): the shape of a masked sum (whether the Mul has a key
+  // mask operand is that Mul's business)
+  bool masked_sum_shape(const std::string& name) const {
+    auto r = producer_.find(name);
+    if (r == producer_.end() || m_.nodes[r->second].op_type != "ReduceSum" || m_.nodes[r->second].inputs.empty()) return false;
+    auto q = producer_.find(m_.nodes[r->second].in(0));
+    return q != producer_.end() && m_.nodes[q->second].op_type == "Mul";
+  }
+
+  bool lower_pool_node(int idx) {
+    const Node& n = m_.nodes[idx];
+    const std::string& op = n.op_type;
+    const std::string who = op + " " + n.name + ": ";
+    auto fail = [&](const std::string& why) { throw std::runtime_error(who + why); };
+    const Val* m = n.inputs.empty() ? nullptr : val_if(n.in(0), Val::KEYVIS);
+    if (m && op == "Unsqueeze" && m->kv_rank == 2 && !m->kv_add) {  // [N, S] -> [N, S, 1]
+      std::vector<int64_t> axes = n.get_ints("axes");
+      if (axes.empty() && n.inputs.size() > 1) ints_of(n.in(1), axes);
+      if (axes.size() != 1 || !(axes[0] == -1 || axes[0] == 2)) return false;  // towards [N, 1, 1, S]: lower_token_node
+      Val o = *m;
+      o.kv_rank = 3;
+      o.kv_last = true;
+      define(n.outputs[0], o);
+      return true;
+    }
+    if (m && m->kv_last && (op == "Unsqueeze" || op == "Reshape" || op == "Sub"))
+      fail("a key mask [N, S, 1] goes only through Expand to [N, S, D], Cast and Not (masked mean pooling)");
+    if (m && m->kv_last && op == "Expand") {
+      std::vector<int64_t> shp;
+      const bool ok = n.inputs.size() == 2 && ints_of(n.in(1), shp) && shp.size() == 3 && (shp[0] == 1 || shp[0] == kBatchDim) &&
+                      (shp[1] == 1 || shp[1] == m->H) && shp[2] >= 1 && !m->kv_D;
+      if (!ok) fail("a key mask [N, S, 1] expands only to [N, S, D]");
+      Val o = *m;
+      o.kv_D = static_cast<int>(shp[2]);
+      define(n.outputs[0], o);
+      return true;
+    }
+    if (op == "Mul" && n.inputs.size() == 2)  // rows x mask
+      for (int side = 0; side < 2; ++side) {
+        const Val* s = val_if(n.in(side), Val::KEYVIS);
+        const Val* x = val_if(n.in(1 - side), Val::ROWS_BF16);
+        if (!s || !x) continue;
+        if (s->kv_add || !s->kv_last || x->rank != 3)
+          fail("rows [N, S, D] are multiplied only by a key mask of the shape [N, S, 1] or [N, S, D] (masked mean pooling)");
+        if (!dense(*x)) fail("the masked rows must be dense");
+        const int S = x->H * x->W;
+        if (s->H != S)
+          fail("the key mask's length " + std::to_string(s->H) + " is not the rows' " + std::to_string(S));
+        if (s->kv_D && s->kv_D != x->logical() && s->kv_D != x->C) fail("the expanded key mask's width is not the rows'");
+        const int r = sole_consumer(n.outputs[0]);
+        std::vector<int64_t> ax;
+        if (r < 0 || m_.nodes[r].op_type != "ReduceSum" || !reduce_axes(m_.nodes[r], ax) || ax.size() != 1 ||
+            !(ax[0] == 1 || ax[0] == -2) || m_.nodes[r].get_int("keepdims", 1) != 0)
+          fail("rows times a key mask feed only ReduceSum(axis 1, keepdims 0), the masked sum over the tokens");
+        Val o = *s;
+        o.kind = Val::POOLV;
+        o.stage = 0;
+        o.buf = x->buf;
+        o.C = x->C;
+        o.cl = x->cl;
+        o.H = S;
+        define(n.outputs[0], o);
+        return true;
+      }
+    if (op == "ReduceSum" && !n.inputs.empty()) {
+      std::vector<int64_t> ax;
+      reduce_axes(n, ax);
+      const bool keep = n.get_int("keepdims", 1) != 0;
+      if (const Val* r = val_if(n.in(0), Val::POOLV)) {  // the masked sum (axes checked by the Mul)
+        if (r->stage != 0) fail("only rows times a key mask are summed over the tokens");
+        const int d = sole_consumer(n.outputs[0]);
+        if (d < 0 || m_.nodes[d].op_type != "Div" || m_.nodes[d].inputs.size() != 2 || m_.nodes[d].in(0) != n.outputs[0] ||
+            m_.nodes[d].in(1) == n.outputs[0])
+          fail("a masked sum over the tokens must be divided by the count of visible tokens (masked mean pooling; sum "
+               "pooling is out of scope)");
+        Val o = *r;
+        o.stage = 1;
+        define(n.outputs[0], o);
+        return true;
+      }
+      if (m) {  // the count of visible tokens
+        const bool form = !m->kv_add && ax.size() == 1 &&
+                          (m->kv_last ? (ax[0] == 1 || ax[0] == -2) && !keep : m->kv_rank == 2 && (ax[0] == 1 || ax[0] == -1) && keep);
+        if (!form)
+          fail("a key mask is summed only over the token axis, to the count of visible tokens [N, D] or [N, 1] (masked "
+               "mean pooling)");
+        std::string cur = n.outputs[0];
+        for (bool closed = false; !closed;) {
+          const int c = sole_consumer(cur);
+          const Node* q = c >= 0 ? &m_.nodes[c] : nullptr;
+          if (q && q->inputs.size() >= 1 && (q->op_type == "Clip" || q->op_type == "Max") &&
+              (q->in(0) == cur || (q->op_type == "Max" && q->inputs.size() == 2 && q->in(1) == cur)))
+            cur = q->outputs[0];  // its bounds are that node's business
+          else if (q && q->op_type == "Div" && q->inputs.size() == 2 && q->in(1) == cur && masked_sum_shape(q->in(0)))
+            closed = true;
+          else
+            fail("the count of a key mask's visible tokens must end, through Clip(min) / Max, as the divisor of the masked "
+                 "sum Mul(rows, mask) -> ReduceSum(axis 1) (masked mean pooling); other uses of a key mask are out of scope");
+        }
+        Val o = *m;
+        o.kind = Val::POOLV;
+        o.stage = 2;
+        o.pool_c = 0.f;
+        define(n.outputs[0], o);
+        return true;
+      }
+    }
+    if (op == "Clip" || op == "Max") {  // lower bound of the count
+      const Val* c = n.inputs.empty() ? nullptr : val_if(n.in(0), Val::POOLV);
+      int side = 0;
+      if (!c && op == "Max" && n.inputs.size() == 2 && (c = val_if(n.in(1), Val::POOLV))) side = 1;
+      if (c) {
+        if (c->stage != 2) fail("only the count of visible tokens is clipped (masked mean pooling)");
+        float lo = 0.f, hi = 3.4e38f;
+        if (op == "Clip") {
+          if (!clip_bounds(n, lo, hi)) fail("bounds must be constants");
+          if (hi < 3.4e38f) fail("a Clip with a max on the count of visible tokens is not supported (only a lower bound)");
+          if (lo == -3.4e38f) lo = 0.f;
+        } else if (n.inputs.size() != 2 || !scalar_init(n.in(1 - side), lo)) {
+          fail("the count of visible tokens is bounded only by a scalar initializer");
+        }
+        if (!(lo >= 0.f)) fail("the lower bound of the count of visible tokens must be >= 0");
+        Val o = *c;
+        o.pool_c = std::max(c->pool_c, lo);
+        define(n.outputs[0], o);
+        return true;
+      }
+    }
+    if (op == "Div" && n.inputs.size() == 2) {
+      const Val* a = val_if(n.in(0), Val::POOLV);
+      const Val* b = val_if(n.in(1), Val::POOLV);
+      if (a || b) {
+        if (!a || !b || a->stage != 1 || b->stage != 2)
+          fail("masked mean pooling divides the masked sum over the tokens by the count of visible tokens, nothing else");
+        if (a->kv_op != b->kv_op || a->kv_c != b->kv_c || a->kv_neg != b->kv_neg || a->kv_trunc != b->kv_trunc)
+          fail("the count is not over the visibility value of the masked sum (different pad tests)");
+        if (b->kv_D && b->kv_D != a->logical() && b->kv_D != a->C) fail("the count's width is not the masked sum's");
+        const Val rows = *a, vis = *a;
+        emit_pool_tokens(n, rows, rows.H, &vis, b->pool_c, n.outputs[0], true, false, 0.f);
+        return true;
+      }
+    }
+    for (const auto& in : n.inputs)
+      if (val_if(in, Val::POOLV))
+        fail("a masked sum / count of visible tokens feeds only Clip(min) / Max and the Div that closes the masked mean");
+    return false;
+  }
+
+  // ReduceL2(x, last axis, keepdims 1) [-> Clip(min = eps) | Max(., eps)] [-> Expand] -> Div(x, .), from
+  // the ReduceL2 node: torch's export of F.normalize.  False with a reason when it is something else.
+  // The Expand's shape is constant or Shape(x); used lists the chain's nodes, the Div last, and
+  // shape_node that Shape (-1: none).
+  bool l2_chain(int ridx, int rank, float& eps, std::string& out, std::vector<int>& used, std::string& why,
+                int& shape_node) const {
+    const Node& r = m_.nodes[ridx];
+    const std::string& x = r.in(0);
+    std::vector<int64_t> ax;
+    if (!reduce_axes(r, ax) || ax.size() != 1 || !(ax[0] == -1 || ax[0] == rank - 1) || r.get_int("keepdims", 1) != 1) {
+      why = "the norm is taken over the last axis with keepdims 1";
+      return false;
+    }
+    used = {ridx};
+    eps = 0.f;
+    shape_node = -1;
+    std::string cur = r.outputs[0];
+    int c = sole_consumer(cur);
+    if (c >= 0 && (m_.nodes[c].op_type == "Clip" || m_.nodes[c].op_type == "Max")) {
+      const Node& q = m_.nodes[c];
+      float lo = 0.f, hi = 3.4e38f;
+      if (q.op_type == "Clip") {
+        if (q.in(0) != cur || !clip_bounds(q, lo, hi) || hi < 3.4e38f) {
+          why = "Clip " + q.name + ": only a constant min (a Clip with a max is not supported)";
+          return false;
+        }
+        if (lo == -3.4e38f) lo = 0.f;
+      } else if (q.inputs.size() != 2 || !scalar_init(other_input(q, cur), lo)) {
+        why = "Max " + q.name + ": only with a scalar initializer";
+        return false;
+      }
+      if (!(lo >= 0.f)) {
+        why = q.op_type + " " + q.name + ": the lower bound of a norm must be >= 0";
+        return false;
+      }
+      eps = lo;
+      used.push_back(c);
+      cur = q.outputs[0];
+      c = sole_consumer(cur);
+    }
+    if (c >= 0 && m_.nodes[c].op_type == "Expand" && m_.nodes[c].in(0) == cur) {
+      std::vector<int64_t> shp;
+      const auto sp = m_.nodes[c].inputs.size() == 2 ? producer_.find(m_.nodes[c].in(1)) : producer_.end();
+      if (sp != producer_.end() && m_.nodes[sp->second].op_type == "Shape" && m_.nodes[sp->second].in(0) == x &&
+          consumers(m_.nodes[sp->second].outputs[0]).size() == 1) {
+        shape_node = sp->second;
+      } else if (m_.nodes[c].inputs.size() != 2 || !ints_of(m_.nodes[c].in(1), shp) || static_cast<int>(shp.size()) != rank) {
+        why = "Expand " + m_.nodes[c].name + ": the norm expands only to the rows' shape";
+        return false;
+      }
+      used.push_back(c);
+      cur = m_.nodes[c].outputs[0];
+      c = sole_consumer(cur);
+    }
+    if (c < 0 || m_.nodes[c].op_type != "Div" || m_.nodes[c].inputs.size() != 2 || m_.nodes[c].in(0) != x ||
+        m_.nodes[c].in(1) != cur) {
+      why = "the norm's only reader must be Div(x, norm)";
+      return false;
+    }
+    used.push_back(c);
+    out = m_.nodes[c].outputs[0];
+    return true;
+  }
+
+  // Every reader of the rank-2 value `x` belongs to one L2 normalisation over its last axis.
+  bool only_l2_normalized(const std::string& x, float& eps, std::string& out, std::vector<int>& used) const {
+    if (graph_outputs_.count(x)) return false;
+    const std::vector<int> cs = consumers(x);
+    if (cs.size() == 1 && m_.nodes[cs[0]].op_type == "LpNormalization" && !done_[cs[0]]) {
+      const Node& l = m_.nodes[cs[0]];
+      const int64_t axis = l.get_int("axis", -1);
+      if (l.get_int("p", 2) != 2 || !(axis == -1 || axis == 1)) return false;  // rejected at that node
+      eps = 0.f;
+      out = l.outputs[0];
+      used = {cs[0]};
+      return true;
+    }
+    for (int r : cs) {
+      std::string why;
+      int shape_node = -1;
+      if (m_.nodes[r].op_type != "ReduceL2" || done_[r] || !l2_chain(r, 2, eps, out, used, why, shape_node)) continue;
+      for (int c : cs)  // x's readers: the ReduceL2, the Div and the Shape for the Expand
+        if (c != r && c != used.back() && c != shape_node) return false;
+      if (shape_node >= 0 && !done_[shape_node]) used.push_back(shape_node);
+      return true;
+    }
+    return false;
+  }
+
+  // LpNormalization / ReduceL2 on rows that are not a pooled vector's only use: POOL_TOKENS with S = 1.
+  void lower_l2norm(int idx) {
+    const Node& n = m_.nodes[idx];
+    const std::string who = n.op_type + " " + n.name + ": ";
+    const Val x = val(n.in(0), n);
+    const int rank = x.rank ? x.rank : 2;
+    float eps = 0.f;
+    std::string out = n.outputs[0];
+    std::vector<int> used;
+    if (n.op_type == "LpNormalization") {
+      const int64_t axis = n.get_int("axis", -1);
+      if (n.get_int("p", 2) != 2) throw std::runtime_error(who + "only p = 2 (L2 normalisation) is supported");
+      if (!(axis == -1 || axis == rank - 1)) throw std::runtime_error(who + "only the last axis is normalised");
+    } else {
+      std::string why;
+      int shape_node = -1;
+      if (!l2_chain(idx, rank, eps, out, used, why, shape_node))
+        throw std::runtime_error(who + "only torch's export of F.normalize, ReduceL2(last axis, keepdims 1) -> Clip(min = eps) "
+                                 "-> [Expand] -> Div(x, .), is supported (" + why + ")");
+    }
+    if (x.kind != Val::ROWS_BF16 || rank != 2 || x.H * x.W != 1 || !dense(x))
+      throw std::runtime_error(who + "only dense rank-2 rows [N, D] are L2-normalised");
+    for (int u : used) done_[u] = true;
+    emit_pool_tokens(n, x, 1, nullptr, 0.f, out, false, true, eps);
+  }
+
+  // One POOL_TOKENS op over the rows x ([S][C] per sample); vis: the key mask of a masked mean (nullptr:
+  // all S rows).  try_norm: an L2 normalisation that is the result's only reader joins the op.
+  void emit_pool_tokens(const Node& n, const Val& x, int S, const Val* vis, float clip_min, std::string out_name,
+                        bool try_norm, bool normalize, float eps) {
+    PlanOp p;
+    p.kind = PlanOp::POOL_TOKENS;
+    p.name = n.name;
+    p.in = x.buf;
+    p.S = S;
+    p.C = x.C;
+    p.Cp = x.logical();
+    p.clip_lo = clip_min;
+    if (vis) {
+      bind_key_test(n.op_type + " " + n.name + ": ", *vis, true);  // the mask multiplies: true = visible
+      p.key_mask = 1;
+      p.in4 = plan_.ops[key_op_].out2;
+      p.in5 = plan_.ops[key_op_].out3;
+    }
+    std::vector<int> used;
+    std::string nout;
+    if (try_norm && only_l2_normalized(out_name, eps, nout, used)) {
+      normalize = true;
+      for (int u : used) done_[u] = true;
+      p.name += "+" + m_.nodes[used[0]].name;
+      out_name = nout;
+    }
+    p.act = normalize ? 1 : 0;
+    p.eps = normalize ? eps : 0.f;
+    p.flops_per_sample = static_cast<double>(S) * p.Cp;
+    Val o;
+    o.kind = Val::ROWS_BF16;
+    o.C = x.C;
+    o.cl = x.cl;
+    o.rank = 2;
+    if (graph_outputs_.count(out_name) && consumers(out_name).empty()) {  // fp32 straight to the output
+      p.out_f32 = kBufGraphOut;
+      o.kind = Val::ROWS_F32;
+      o.buf = kBufGraphOut;
+    } else {
+      p.out = new_buf(static_cast<size_t>(x.C) * 2);
+      o.buf = p.out;
+    }
+    define(out_name, o);
+    add_op(std::move(p));
   }
 
   // ---- attention bias / mask folding --------------------------------------------------------------
@@ -3223,6 +3565,7 @@ class Planner {
   std::unordered_map<std::string, int> vid_;
   std::unordered_map<std::string, std::vector<int>> consumers_;
   std::unordered_set<std::string> graph_outputs_;
+  std::unordered_map<std::string, int> producer_;  // value name -> the node writing it
   std::unordered_map<std::string, int> prepped_;
   std::unordered_map<std::string, std::array<int64_t, 4>> folded_pad_;  // Pad output -> (t, l, b, r) for its conv
   std::vector<bool> done_;

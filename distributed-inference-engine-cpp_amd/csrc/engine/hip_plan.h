@@ -31,9 +31,16 @@
 //    Not / Cast / Unsqueeze / Reshape / Sub(1, m) / Mul(m, c <= -1e4)) consumed on attention scores
 //    as Where(vis, scores, f), Where(hidden, f, scores) or Add(scores, additive) becomes the
 //    attention op's key_mask flag: EMBED_TOKENS writes the per-sample key data once per forward.
-//    Rejected with a report line: key mask + causal, a visibility value used elsewhere (masked
-//    mean pooling), Gather on another axis or from a non-initializer table, mask shapes other than
+//    Rejected with a report line: key mask + causal, a visibility value used in any other way,
+//    Gather on another axis or from a non-initializer table, mask shapes other than
 //    [N, 1, 1, S].  A second graph input (attention_mask / token_type_ids tensors) is out of scope.
+//  * sentence embedders: the masked mean over the tokens, Mul(rows, m) -> ReduceSum(axis 1) divided by
+//    ReduceSum(m, axis 1) [-> Clip(min) / Max] with m = the same visibility value unsqueezed at the
+//    last axis [-> Expand to [N, S, D]] -> Cast, is one POOL_TOKENS op reading the key data; an L2
+//    normalisation of rank-2 rows over the last axis (LpNormalization p = 2, or torch's F.normalize
+//    export ReduceL2 -> Clip(min = eps) -> [Expand] -> Div) joins that op when the pooled vector has
+//    no other reader and is a POOL_TOKENS op with S = 1 anywhere else.  As the graph output the op
+//    writes fp32 straight into the output buffer.  Sum / max / last-token pooling: out of scope.
 //    Sibling Q/K/V MatMuls become one GEMM (N = 3*D); MatMul -> Add(bias) -> erf-GELU and
 //    MatMul -> Add(bias) -> Add(residual) fold into the GEMM epilogue; cls Expand/Concat + position
 //    Add -> one token-assembly kernel; LayerNormalization and Gather(token) -> row kernels.
@@ -78,11 +85,15 @@ struct PlanOp {
              // in2 [gidx][ld[1]]; Cp = logical N
     GAP_FC,  // global pool (gidx = mode) of in [H*W][C] + the 1x1 GEMM that is its only reader, in one
              // launch: out_f32 [Cp] = act(pool . w + bias); conv describes the GEMM (Kpad, wplane)
-    EMBED_TOKENS  // token ids (the fp32 graph input [S], in = -2) -> rows: out [S][C] = table[idx(id)] + pos + type
+    EMBED_TOKENS,  // token ids (the fp32 graph input [S], in = -2) -> rows: out [S][C] = table[idx(id)] + pos + type
                   // with w_off = table [gidx = V][C] f32, shift_off = pos [S][C], bias_off = type [C] (C = stored
                   // width, Cp = the model's); key data for key-masked attention when out2 >= 0: out2 = kvis
                   // f32 [S rounded up to 32], out3 = kend (one int), pad test visible = ((in_relu ? trunc(id)
                   // : id) OP clip_lo) != is_max with OP = act (0 Equal, 1 Greater, 2 Less)
+    POOL_TOKENS  // rows in [S][C] (Cp logical columns) -> one vector: out [C] (bf16 / split) or out_f32 [Cp] (the
+                 // graph output).  key_mask = 1: the mean over the visible tokens, sum / max(count, clip_lo),
+                 // with in4 / in5 = the EMBED_TOKENS op's kvis / kend; else the mean of all S rows.
+                 // act = 1: then v / max(||v||_2, eps).  S = 1, act = 1: a row L2 normalisation
   } kind;
   std::string name;
   // buffers (-1 = none).  -2 = the graph input (f32 NCHW), -3 = the graph output (f32).

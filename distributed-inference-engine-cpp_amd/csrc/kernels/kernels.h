@@ -403,6 +403,22 @@ hipError_t embed_tokens(const float* ids, const float* table, int ldt, const flo
                         uint16_t* out, int B, int S, int V, int C, hipStream_t s, int split = 0, float* kvis = nullptr,
                         int* kend = nullptr, int Sp = 0, int pad_op = 0, float pad_c = 0.f, int pad_neg = 1,
                         int pad_trunc = 0);
+// Token pooling + L2 normalisation of bf16 / split rows x [B][S][C] (C % 8 == 0 stored, D <= C logical
+// columns) -> one vector per sample: out (nullable) bf16 / split [B][C] with the pad columns 0,
+// out_f32 (nullable) [B][D].
+//  * kvis / kend (both or neither; embed_tokens' key data, Sp = S rounded up to 32): the mean runs
+//    over the visible tokens only, sum / max(count, clip_min); a sample with none gets zeros (ONNX:
+//    NaN).  Without them: the mean of all S rows.
+//  * normalize != 0: then v / max(||v||_2, eps) over the D columns (0 where that is 0 / 0).  With
+//    S = 1 this is a row normalisation alone.
+// One launch, capturable.  normalize with C > 64 hands the row over between its column blocks:
+// ws >= pool_tokens_ws_bytes(B, C) bytes and B counters holding 0 (left at 0), neither shared with a
+// launch that may run at the same time.  Anything else: hipErrorInvalidValue, nothing launched.
+size_t pool_tokens_ws_bytes(int B, int C);
+hipError_t pool_tokens(const uint16_t* x, uint16_t* out, float* out_f32, int B, int S, int C, int D, const float* kvis,
+                       const int* kend, int Sp, float clip_min, int normalize, float eps, hipStream_t s,
+                       const long long* live = nullptr, int split = 0, float* ws = nullptr, size_t ws_bytes = 0,
+                       int* counters = nullptr, int counters_n = 0);
 int token_index_host(float x, int V);  // k::token_index on the host (tests)
 bool token_visible_host(float x, int op, float c, int neg, int trunc);  // k::token_visible on the host
 

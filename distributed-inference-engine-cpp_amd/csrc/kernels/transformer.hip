@@ -262,6 +262,130 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(
   }
 }
 
+// Token pooling and L2 normalisation of rows x [B][S][C] -> one vector per sample (sentence
+// embedders): the mean over the tokens -- with the key data embed_tokens_kernel wrote, over the
+// VISIBLE tokens only, sum / max(count, clip_min) -- then, optionally, v / max(||v||_2, eps) over the
+// D logical columns.  S = 1 with normalize is a plain row normalisation.
+// Block (column slice j, sample b): 64 columns x all tokens; 8 column threads (8 columns each, one
+// 16-byte load per plane) x 32 token slices sum and count in registers, the slices meet in LDS and
+// are added in slice order.  A masked sample walks only tokens s < kend[b] and skips those whose
+// kvis is -inf (holes); a sample with no visible token gets zeros.  One block per sample would leave
+// one CU streaming S * C * 4 bytes at small batch.
+// normalize with more than one column slice: the pooled values and the slice's sum of squares leave
+// with write-through (sc1) stores, every wave drains them, one lane takes the sample's agent-scope
+// ticket, and the last slice to arrive makes one acquire, adds the sums of squares in slice order
+// (deterministic) and writes the whole normalised row -- gap_fc_kernel's hand-off; nobody spins, the
+// ticket is left at 0.  ws: [B][C] pooled values then [B][gridDim.x] sums of squares.
+// out (nullable): bf16 / split rows [B][C], pad columns 0; out_f32 (nullable): [B][D].
+constexpr int kPoolCols = 64;
+constexpr int kPoolSlices = 32;
+constexpr int kCpolSc1Pool = 16;
+
+__global__ __launch_bounds__(256) void pool_tokens_kernel(const uint16_t* __restrict__ x, uint16_t* __restrict__ out,
+                                                          float* __restrict__ out_f32, int S, int C, int D,
+                                                          const float* __restrict__ kvis, const int* __restrict__ kend,
+                                                          int Sp, float clip_min, int normalize, float eps,
+                                                          const long long* __restrict__ live, int split, float* ws,
+                                                          int* counters) {
+  __shared__ float part[kPoolSlices][kPoolCols + 1];
+  __shared__ float cnts[kPoolSlices];
+  __shared__ int flag;
+  const int b = blockIdx.y, B = gridDim.y, NS = gridDim.x, tid = threadIdx.x;
+  if (live && b >= *live) return;  // whole block: before any barrier
+  const long long xplane = static_cast<long long>(B) * S * C, oplane = static_cast<long long>(B) * C;
+  const int cg = tid & 7, ts = tid >> 3;
+  const int c8 = blockIdx.x * kPoolCols + cg * 8;
+  const int send = kend ? max(0, min(kend[b], S)) : S;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float cnt = 0.f;
+  if (c8 < C) {
+    const uint16_t* src = x + static_cast<long long>(b) * S * C + c8;
+    const float* kv = kvis ? kvis + static_cast<long long>(b) * Sp : nullptr;
+#pragma unroll 4
+    for (int s = ts; s < send; s += kPoolSlices) {
+      if (kv && kv[s] != 0.f) continue;  // a hole
+      float v[8];
+      load8v(src + static_cast<long long>(s) * C, xplane, split != 0, v);
+#pragma unroll
+      for (int t = 0; t < 8; ++t) acc[t] += v[t];
+      cnt += 1.f;
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 8; ++t) part[ts][cg * 8 + t] = acc[t];
+  if (cg == 0) cnts[ts] = cnt;  // column group 0 of a slice is always inside C
+  __syncthreads();
+  const int c = blockIdx.x * kPoolCols + tid;  // threads 0..63 (wave 0): one column each
+  float v = 0.f;
+  if (tid < kPoolCols) {
+    float sum = 0.f, n = 0.f;
+#pragma unroll
+    for (int k = 0; k < kPoolSlices; ++k) {
+      sum += part[k][tid];
+      n += cnts[k];
+    }
+    v = n > 0.f && c < D ? sum / fmaxf(n, clip_min) : 0.f;
+  }
+  if (!normalize) {
+    if (tid < kPoolCols) {
+      if (out && c < C) store1v(out + static_cast<long long>(b) * C + c, oplane, split != 0, v);
+      if (out_f32 && c < D) out_f32[static_cast<long long>(b) * D + c] = v;
+    }
+    return;
+  }
+  if (NS == 1) {  // the whole row is in this block: no hand-off
+    if (tid < kPoolCols) {
+      const float nrm = fmaxf(sqrtf(wave_sum(v * v)), eps);
+      const float r = nrm > 0.f ? v / nrm : 0.f;
+      if (out && c < C) store1v(out + static_cast<long long>(b) * C + c, oplane, split != 0, r);
+      if (out_f32 && c < D) out_f32[static_cast<long long>(b) * D + c] = r;
+    }
+    return;
+  }
+  const __amdgpu_buffer_rsrc_t wsr = __builtin_amdgcn_make_buffer_rsrc(ws, 0, 0x7fffffff, 0x00020000);
+  const unsigned ss_base = static_cast<unsigned>(static_cast<long long>(B) * C * 4);  // byte offset of the sums of squares
+  if (tid < kPoolCols) {
+    const float ss = wave_sum(v * v);
+    if (c < C)
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), wsr,
+                                            static_cast<unsigned>((static_cast<long long>(b) * C + c) * 4), 0, kCpolSc1Pool);
+    if (tid == 0)
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ss), wsr,
+                                            ss_base + static_cast<unsigned>((b * NS + static_cast<int>(blockIdx.x)) * 4), 0,
+                                            kCpolSc1Pool);
+  }
+  // hand-off (gap_fc_kernel's form): every wave drains its write-through stores, one lane takes the
+  // sample's ticket; the last arriver's lane runs ONE agent acquire and waits for it before the
+  // barrier that releases the other waves onto the partials, which are read with sc1 loads
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    const int prev = __hip_atomic_fetch_add(counters + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int last = prev == NS - 1;
+    if (last) {
+      __hip_atomic_store(counters + b, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    flag = last;
+  }
+  __syncthreads();
+  if (!flag) return;
+  float ss = 0.f;
+  for (int j = 0; j < NS; ++j)  // slice order: the same sum whichever block arrives last
+    ss += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+                                        wsr, ss_base + static_cast<unsigned>((b * NS + j) * 4), 0, kCpolSc1Pool));
+  const float nrm = fmaxf(sqrtf(ss), eps);
+  for (int cc = tid; cc < C; cc += 256) {
+    const float u = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+                                                  wsr, static_cast<unsigned>((static_cast<long long>(b) * C + cc) * 4), 0,
+                                                  kCpolSc1Pool));
+    const float r = nrm > 0.f ? u / nrm : 0.f;
+    if (out) store1v(out + static_cast<long long>(b) * C + cc, oplane, split != 0, r);
+    if (out_f32 && cc < D) out_f32[static_cast<long long>(b) * D + cc] = r;
+  }
+}
+
 // ---- fused attention ------------------------------------------------------------------------------
 // FlashAttention-style, on v_mfma_f32_32x32x16_bf16, for head dim 64 and S <= 256 (ViT: 197 tokens).
 // A block = one (image b, head h) pair, 8 waves (two per SIMD); wave w owns query tile w (32 queries).
@@ -881,6 +1005,28 @@ hipError_t embed_tokens(const float* ids, const float* table, int ldt, const flo
   const int eblocks = grid_for(static_cast<long long>(B) * S * (C / 8));
   hipLaunchKernelGGL(embed_tokens_kernel, dim3(eblocks + (kvis ? B : 0)), dim3(256), 0, s, ids, table, ldt, pos, type,
                      out, B, S, V, C, split, eblocks, kvis, kend, Sp, pad_op, pad_c, pad_neg, pad_trunc);
+  return hipGetLastError();
+}
+
+size_t pool_tokens_ws_bytes(int B, int C) {
+  return static_cast<size_t>(B) * (C + (C + kPoolCols - 1) / kPoolCols) * 4;
+}
+
+hipError_t pool_tokens(const uint16_t* x, uint16_t* out, float* out_f32, int B, int S, int C, int D, const float* kvis,
+                       const int* kend, int Sp, float clip_min, int normalize, float eps, hipStream_t s,
+                       const long long* live, int split, float* ws, size_t ws_bytes, int* counters, int counters_n) {
+  auto misaligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; };
+  if (B <= 0 || S <= 0 || C <= 0 || C % 8 || D <= 0 || D > C || !x || (!out && !out_f32) || misaligned(x) || B > 65535 ||
+      !(clip_min >= 0.f) || !(eps >= 0.f))
+    return hipErrorInvalidValue;
+  if ((kvis == nullptr) != (kend == nullptr)) return hipErrorInvalidValue;
+  if (kvis && Sp != (S + 31) / 32 * 32) return hipErrorInvalidValue;
+  const int ns = (C + kPoolCols - 1) / kPoolCols;
+  if (normalize && ns > 1 &&
+      (!ws || !counters || counters_n < B || pool_tokens_ws_bytes(B, C) > ws_bytes || pool_tokens_ws_bytes(B, C) >> 31))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pool_tokens_kernel, dim3(ns, B), dim3(256), 0, s, x, out, out_f32, S, C, D, kvis, kend, Sp, clip_min,
+                     normalize, eps, live, split, ws, counters);
   return hipGetLastError();
 }
 

@@ -45,6 +45,13 @@ mix a ResNet / ViT never exercises, random weights, written by the in-tree ONNX 
 * `bert_ids_hf` the same at 160 tokens (two query blocks, five key tiles) and 4 heads of 32, with a
               token-type row, a per-head relative-position table and the HF extended attention mask
               Add(scores, (1 - Cast(Greater(ids, 0))) * -10000): table and key mask together.
+* `sbert_ids`  a sentence embedder: the `bert_ids` body, then the sentence-transformers export -- the
+              visibility mask Unsqueeze(-1) -> Expand -> Cast, Mul with the last hidden states, ReduceSum
+              over the tokens, divided by the clipped count of visible tokens -- and torch's
+              F.normalize (ReduceL2 -> Clip(1e-12) -> Expand -> Div).  Output [N, 128], unit length.
+* `sbert_ids_hf` the `bert_ids_hf` body with the mask left unexpanded ([N, S, 1] on the rows, an [N, 1]
+              count) and LpNormalization.
+* `sbert_cls`  the `bert_ids` body, the CLS token, LpNormalization (no mask in the pooling).
 `synthetic_input(model, batch)` gives inputs of the right shape (token-id models: float32 ids in
 [1, V), sample i padded with 0 past a length that cycles through 1, 32, S, 45, 33, every third sample
 with one interior pad id).  The CPU executor is the fp32
@@ -78,10 +85,13 @@ SPECS = {
     "bert_keymask": dict(seq=40, dim=128, heads=2, ffn=256, layers=2, classes=3, masked_keys=9),
     "bert_ids": dict(seq=48, dim=128, heads=2, ffn=256, layers=2, classes=3, vocab=1000, pad=0),
     "bert_ids_hf": dict(seq=160, dim=128, heads=4, ffn=256, layers=2, classes=3, vocab=1000, pad=0),
+    "sbert_ids": dict(seq=48, dim=128, heads=2, ffn=256, layers=2, vocab=1000, pad=0),
+    "sbert_ids_hf": dict(seq=160, dim=128, heads=4, ffn=256, layers=2, vocab=1000, pad=0),
+    "sbert_cls": dict(seq=48, dim=128, heads=2, ffn=256, layers=2, vocab=1000, pad=0),
 }
 
 MASKED = ("gpt_causal", "bert_relpos", "bert_window", "bert_keymask")
-TOKEN_IDS = ("bert_ids", "bert_ids_hf")
+TOKEN_IDS = ("bert_ids", "bert_ids_hf", "sbert_ids", "sbert_ids_hf", "sbert_cls")
 
 
 def _rng(seed):
@@ -292,14 +302,16 @@ def build_token_encoder(seed: int = 0, opset: int = 17, spec: str = "bert_ids",
                         int_input: bool = False) -> Tuple[bytes, Dict[str, np.ndarray]]:
     """Token-id encoders (`bert_ids`, `bert_ids_hf`): the graph input is [N, S] token ids carried as
     numbers (declared FLOAT, or INT64 with int_input), embedded by a Gather, and the attention mask
-    is computed from the ids themselves (pad id 0).  Returns (model bytes, initializers)."""
+    is computed from the ids themselves (pad id 0).  The sentence embedders (`sbert_ids`,
+    `sbert_ids_hf`, `sbert_cls`) end in a pooled, L2-normalised vector [N, D] instead of the CLS
+    classifier.  Returns (model bytes, initializers)."""
     from ..utils.onnx_writer import INT64
 
     s = SPECS[spec]
     rng = _rng(seed)
     S, D, H, F, V = s["seq"], s["dim"], s["heads"], s["ffn"], s["vocab"]
     hd = D // H
-    hf = spec == "bert_ids_hf"
+    hf = spec in ("bert_ids_hf", "sbert_ids_hf")
     g = GraphBuilder(name=spec)
     x = g.input("input_ids", ["N", S], elem_type=INT64) if int_input else g.input("input_ids", ["N", S])
     ids = x if int_input else g.node("Cast", [x], name="ids_int", to=INT64)
@@ -317,14 +329,14 @@ def build_token_encoder(seed: int = 0, opset: int = 17, spec: str = "bert_ids",
     half = g.const(np.array(0.5, np.float32), "half")
     axes12 = g.const(np.array([1, 2], np.int64), "mask_axes")
     if hf:  # HF: extended = (1 - mask[:, None, None, :]) * -10000, mask = ids > 0, from the float input
-        m = g.node("Cast", [g.node("Greater", [x, g.const(np.array(0, np.int64 if int_input else np.float32), "pad_id")],
-                                   name="attention_mask")], name="attention_mask_f", to=1)
-        m = g.node("Unsqueeze", [m, axes12], name="extended_mask")
+        mask_f = g.node("Cast", [g.node("Greater", [x, g.const(np.array(0, np.int64 if int_input else np.float32), "pad_id")],
+                                        name="attention_mask")], name="attention_mask_f", to=1)
+        m = g.node("Unsqueeze", [mask_f, axes12], name="extended_mask")
         key_term = g.node("Mul", [g.node("Sub", [one, m], name="inverted_mask"),
                                   g.const(np.array(-10000.0, np.float32), "mask_value")], name="additive_mask")
     else:  # hidden = ids == pad on the integer ids
-        hidden = g.node("Unsqueeze", [g.node("Equal", [ids, g.const(np.array(s["pad"], np.int64), "pad_id")],
-                                             name="is_pad"), axes12], name="pad_mask")
+        is_pad = g.node("Equal", [ids, g.const(np.array(s["pad"], np.int64), "pad_id")], name="is_pad")
+        hidden = g.node("Unsqueeze", [is_pad, axes12], name="pad_mask")
         fill = g.const(np.array(-np.inf, np.float32), "mask_fill")
 
     def linear(inp, name, fin, fout):
@@ -366,12 +378,45 @@ def build_token_encoder(seed: int = 0, opset: int = 17, spec: str = "bert_ids",
         t = g.node("Add", [g.node("Erf", [t], name=p + "gelu/erf"), one], name=p + "gelu/add")
         t = g.node("Mul", [g.node("Mul", [m1, t], name=p + "gelu/mul"), half], name=p + "gelu/half")
         h = ln(g.node("Add", [linear(t, p + "output", F, D), h], name=p + "residual2"), p + "ln2")
+    if spec.startswith("sbert"):
+        y = _sentence_head(g, spec, h, None if hf else is_pad, mask_f if hf else None)
+        g.output(y, ["N", D])
+        return g.model_proto(opset=opset), dict(g.initializers)
     cls = g.node("Gather", [h, g.const(np.array(0, np.int64), "cls_index")], name="cls_token", axis=1)
     w = g.init("classifier.weight", _lin(rng, D, (s["classes"], D)))
     b = g.init("classifier.bias", (0.1 * rng.standard_normal(s["classes"])).astype(np.float32))
     y = g.node("Gemm", [cls, w, b], name="classifier", transB=1)
     g.output(y, ["N", s["classes"]])
     return g.model_proto(opset=opset), dict(g.initializers)
+
+
+def _sentence_head(g, spec, h, is_pad, mask_f):
+    """The pooling + normalisation tail of the sentence embedders on the last hidden states h [N, S, D]."""
+    last = g.const(np.array([-1], np.int64), "last_axis")
+    tokens = g.const(np.array([1], np.int64), "token_axis")
+    if spec == "sbert_cls":  # the CLS token, LpNormalization
+        cls = g.node("Gather", [h, g.const(np.array(0, np.int64), "cls_index")], name="cls_token", axis=1)
+        return g.node("LpNormalization", [cls], name="normalize", axis=-1, p=2)
+    if spec == "sbert_ids_hf":  # the mask stays [N, S, 1] on the rows; an [N, 1] count; LpNormalization
+        summed = g.node("ReduceSum", [g.node("Mul", [h, g.node("Unsqueeze", [mask_f, last], name="pool_mask")],
+                                             name="masked_states"), tokens], name="masked_sum", keepdims=0)
+        count = g.node("Clip", [g.node("ReduceSum", [mask_f, tokens], name="visible_count", keepdims=1),
+                                g.const(np.array(1e-9, np.float32), "count_min")], name="count_clamp")
+        return g.node("LpNormalization", [g.node("Div", [summed, count], name="mean_pool")], name="normalize", axis=1, p=2)
+    # sentence-transformers: mask.unsqueeze(-1).expand(h.size()).float(); sum(h * m, 1) / clamp(m.sum(1), 1e-9);
+    # then F.normalize(p=2, dim=1): x / clamp(norm(x), 1e-12).expand_as(x)
+    vis = g.node("Not", [is_pad], name="visible")
+    m = g.node("Expand", [g.node("Unsqueeze", [vis, last], name="pool_mask"), g.node("Shape", [h], name="states_shape")],
+               name="pool_mask_expanded")
+    m = g.node("Cast", [m], name="pool_mask_f", to=1)
+    summed = g.node("ReduceSum", [g.node("Mul", [h, m], name="masked_states"), tokens], name="masked_sum", keepdims=0)
+    count = g.node("Clip", [g.node("ReduceSum", [m, tokens], name="visible_count", keepdims=0),
+                            g.const(np.array(1e-9, np.float32), "count_min")], name="count_clamp")
+    pooled = g.node("Div", [summed, count], name="mean_pool")
+    norm = g.node("Clip", [g.node("ReduceL2", [pooled], name="norm", axes=[-1], keepdims=1),
+                           g.const(np.array(1e-12, np.float32), "norm_eps")], name="norm_clamp")
+    norm = g.node("Expand", [norm, g.node("Shape", [pooled], name="pooled_shape")], name="norm_expanded")
+    return g.node("Div", [pooled, norm], name="normalize")
 
 
 def build_se_cnn(seed: int = 0, opset: int = 13) -> Tuple[bytes, Dict[str, np.ndarray]]:
@@ -619,7 +664,10 @@ BUILDERS = {"mlp": build_mlp, "bert": build_bert, "se_cnn": build_se_cnn, "ratio
             "bert_window": lambda seed=0: build_masked_encoder(seed, spec="bert_window"),
             "bert_keymask": lambda seed=0: build_masked_encoder(seed, spec="bert_keymask"),
             "bert_ids": lambda seed=0: build_token_encoder(seed, spec="bert_ids"),
-            "bert_ids_hf": lambda seed=0: build_token_encoder(seed, spec="bert_ids_hf")}
+            "bert_ids_hf": lambda seed=0: build_token_encoder(seed, spec="bert_ids_hf"),
+            "sbert_ids": lambda seed=0: build_token_encoder(seed, spec="sbert_ids"),
+            "sbert_ids_hf": lambda seed=0: build_token_encoder(seed, spec="sbert_ids_hf"),
+            "sbert_cls": lambda seed=0: build_token_encoder(seed, spec="sbert_cls")}
 
 
 def build_onnx(name: str, seed: int = 0) -> bytes:

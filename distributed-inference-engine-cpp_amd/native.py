@@ -730,6 +730,11 @@ def _sig_kernels():
     L.die_kern_attention_keymask.argtypes = [u64] * 4 + [i] * 8 + [C.c_float, u64, i, u64, i, i, i, u64, u64]
     L.die_kern_embed_tokens.restype = i
     L.die_kern_embed_tokens.argtypes = [u64, u64, i, u64, u64, u64, i, i, i, i, u64, i, u64, u64, i, i, C.c_float, i, i]
+    L.die_kern_pool_tokens.restype = i
+    L.die_kern_pool_tokens.argtypes = [u64, u64, u64, i, i, i, i, u64, u64, i, C.c_float, i, C.c_float, u64, u64, i,
+                                       u64, u64, u64, i]
+    L.die_kern_pool_tokens_ws_bytes.restype = u64
+    L.die_kern_pool_tokens_ws_bytes.argtypes = [i, i]
     L.die_token_index.restype = i
     L.die_token_index.argtypes = [C.c_float, i]
     L.die_kern_set_attention_variant.restype = None

@@ -418,6 +418,38 @@ def key_mask_data(visible):
     return kvis, kend
 
 
+def pool_tokens(x, key_mask=None, clip_min=0.0, normalize=False, eps=1e-12, split=False, out_f32=True, dim=None,
+                counters=None):
+    """Token pooling + L2 normalisation: x [B, S, C] (bf16, or fp32 with split) -> one vector per sample.
+    key_mask: the (kvis, kend) pair of key_mask_data() / embed_tokens(): the mean runs over the visible
+    tokens only, sum / max(count, clip_min), and a sample with none gets zeros; None: the mean of all S
+    rows.  normalize: then v / max(||v||_2, eps) over the first `dim` columns (default C; the rest
+    are stored pad columns, written 0).  Returns (rows [B, C] bf16 -- fp32 from the hi / lo planes
+    with split --, fp32 [B, dim] or None).  counters: an int32 tensor of >= B zeros for the
+    cross-block hand-off of a normalised row wider than 64 columns (default: a fresh one); the kernel
+    leaves it at 0."""
+    import torch
+
+    B, S, C = x.shape
+    D = C if dim is None else int(dim)
+    dev = x.device
+    out = torch.empty(((2,) if split else ()) + (B, C), dtype=torch.bfloat16, device=dev)
+    out32 = torch.empty((B, D), dtype=torch.float32, device=dev) if out_f32 else None
+    xin = _in(x, split)
+    kvis, kend = key_mask if key_mask is not None else (None, None)
+    Sp = 0 if kvis is None else int(kvis.shape[1])
+    L = native.kernels()
+    ws_bytes = int(L.die_kern_pool_tokens_ws_bytes(B, C))
+    ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=dev)
+    if counters is None:
+        counters = torch.zeros((B,), dtype=torch.int32, device=dev)
+    rc = L.die_kern_pool_tokens(_ptr(xin), _ptr(out), _ptr(out32), B, S, C, D, _ptr(kvis), _ptr(kend), Sp, float(clip_min),
+                                int(normalize), float(eps), _stream(), 0, int(split), _ptr(ws), ws_bytes,
+                                _ptr(counters), int(counters.numel()))
+    _check(rc, "pool_tokens")
+    return _out(out, split), out32
+
+
 _LOG2E = 1.4426950408889634
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-op device time of one forward on the HIP engine (events around eager launches of the tuned
 kernels), written as a markdown table + JSON.  Usage: op_profile.py --arch resnet50|vit_b16 --batch 32
-Token-id models (--arch bert_ids|bert_ids_hf) are profiled on a batch of ids fed first: --ids full
+Token-id models (--arch bert_ids|bert_ids_hf|sbert_ids|sbert_ids_hf|sbert_cls) are profiled on a batch of ids fed first: --ids full
 (every sequence full length) or synthetic (models/generic.py synthetic lengths and holes)."""
 import argparse
 import json
@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=["resnet50", "vit_b16", "bert_ids", "bert_ids_hf"], default="resnet50")
+    ap.add_argument("--arch", choices=["resnet50", "vit_b16", "bert_ids", "bert_ids_hf", "sbert_ids", "sbert_ids_hf", "sbert_cls"], default="resnet50")
     ap.add_argument("--ids", choices=["full", "synthetic"], default="full", help="token-id models: the profiled batch")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--iters", type=int, default=20)
@@ -41,7 +41,7 @@ def main():
     import die_amd  # noqa: F401
     from die_amd import native
 
-    token_ids = a.arch.startswith("bert_ids")
+    token_ids = a.arch.startswith(("bert_ids", "sbert_"))
     if token_ids:
         from die_amd.models import generic as m
 
