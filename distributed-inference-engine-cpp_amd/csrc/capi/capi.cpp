@@ -95,7 +95,6 @@ EngineOptions engine_opts(const Json& j) {
   e.coarse_buckets = jget<bool>(j, "coarse_buckets", e.coarse_buckets);
   e.pace_lead_scale = jget<double>(j, "pace_lead_scale", e.pace_lead_scale);
   e.completion_poll_us = jget<int>(j, "completion_poll_us", e.completion_poll_us);
-  e.bn_on_load = jget<bool>(j, "bn_on_load", e.bn_on_load);
   e.fuse_pairs = jget<bool>(j, "fuse_pairs", e.fuse_pairs);
   e.fuse_stem_pool = jget<bool>(j, "fuse_stem_pool", e.fuse_stem_pool);
   e.fuse_gap_fc = jget<bool>(j, "fuse_gap_fc", e.fuse_gap_fc);

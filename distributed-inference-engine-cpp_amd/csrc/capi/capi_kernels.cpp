@@ -364,8 +364,15 @@ char* die_hybrid_partition(const char* model_path, int max_batch, int split, cha
 // bit 4 LayerNorm statistics from the producing GEMM's epilogue
 char* die_plan_summary(const char* model_path, int max_batch, int side_branches, int split, int fuse, char** err) {
   try {
-    Plan p = build_plan(onnx::load_onnx(model_path), max_batch, side_branches != 0, split != 0, false, (fuse & 1) != 0,
-                        (fuse & 2) != 0, (fuse & 4) != 0, (fuse & 8) != 0, (fuse & 16) != 0);
+    PlanOptions po;
+    po.side_branches = side_branches != 0;
+    po.split = split != 0;
+    po.fuse_pairs = (fuse & 1) != 0;
+    po.fuse_stem_pool = (fuse & 2) != 0;
+    po.fuse_gap_fc = (fuse & 4) != 0;
+    po.fold_layernorm = (fuse & 8) != 0;
+    po.ln_stats_epilogue = (fuse & 16) != 0;
+    Plan p = build_plan(onnx::load_onnx(model_path), max_batch, po);
     Json j = Json::object();
     j["summary"] = p.summary();
     j["arena_bytes"] = static_cast<long long>(p.arena_bytes);
@@ -404,7 +411,6 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
         e["relu"] = o.conv.relu;
         e["residual"] = o.in2 >= 0;
         e["dual_store"] = o.out2 >= 0;
-        e["preact_on_load"] = o.in_scale_off != SIZE_MAX;
         e["store_main"] = o.out >= 0 || o.out_f32 != -1;
         e["relu2"] = o.conv.relu2;
         e["act"] = o.conv.relu;
@@ -417,7 +423,7 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
         e["causal"] = o.causal != 0;
         e["key_mask"] = o.key_mask != 0;  // the request's padding mask (key data from the embed_tokens op)
         if (o.bias_heads) {  // the folded table, back in natural units: sum of its finite entries, count of -inf
-          const int Sp = (o.S + 31) / 32 * 32;
+          const int Sp = kern::key_pitch(o.S);
           const float* t = reinterpret_cast<const float*>(p.params.data() + o.bias_off);
           double sum = 0;
           long long masked = 0;
@@ -438,18 +444,18 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
         e["positions"] = o.shift_off != SIZE_MAX;
         e["token_type"] = o.bias_off != SIZE_MAX;
         e["key_data"] = o.out2 >= 0;
-        if (o.out2 >= 0) {  // visible = ((trunc ? trunc(id) : id) op c) != neg
+        if (o.out2 >= 0) {
           static const char* cmp[] = {"equal", "greater", "less"};
-          e["pad_op"] = cmp[o.act];
-          e["pad_value"] = static_cast<double>(o.clip_lo);
-          e["pad_negated"] = o.is_max != 0;
-          e["pad_truncated"] = o.in_relu != 0;
+          e["pad_op"] = cmp[o.pad.op];
+          e["pad_value"] = static_cast<double>(o.pad.value);
+          e["pad_negated"] = o.pad.negated;
+          e["pad_truncated"] = o.pad.truncated;
         }
       }
       if (o.kind == PlanOp::POOL_TOKENS) {
         e["masked"] = o.key_mask != 0;  // mean over the visible tokens (key data from the embed_tokens op)
-        e["normalize"] = o.act != 0;
-        e["clip_min"] = static_cast<double>(o.clip_lo);
+        e["normalize"] = o.normalize;
+        e["clip_min"] = static_cast<double>(o.count_min);
         e["eps"] = static_cast<double>(o.eps);
         e["seq"] = o.S;
         e["dim"] = o.Cp;

@@ -288,7 +288,6 @@ Json engine_options_json(const EngineOptions& o) {
   j["coarse_buckets"] = o.coarse_buckets;
   j["pace_lead_scale"] = o.pace_lead_scale;
   j["completion_poll_us"] = o.completion_poll_us;
-  j["bn_on_load"] = o.bn_on_load;
   j["fuse_pairs"] = o.fuse_pairs;
   j["fuse_stem_pool"] = o.fuse_stem_pool;
   j["fuse_gap_fc"] = o.fuse_gap_fc;

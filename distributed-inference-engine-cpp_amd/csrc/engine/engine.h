@@ -237,7 +237,6 @@ struct EngineOptions {
   bool coarse_buckets = false;    // sqrt(2) bucket steps throughout (fewer graphs, faster cold start)
   double pace_lead_scale = 1.0;   // != 1: pacing lead = measured input time x this (< 1 dispatches later)
   int completion_poll_us = 0;     // > 0: sleep-poll each batch's D2H event instead of hipEventSynchronize
-  bool bn_on_load = false;        // bf16 plans: next unit's BN+ReLU applied on the 1x1 conv operand load
   bool fuse_pairs = true;         // expand conv + next reduce conv -> one CONV_PAIR launch (kernels/conv_pair.hip)
   bool fuse_stem_pool = true;     // stem conv + max pool (+ its BN/ReLU) -> one launch (kernels/stem.hip)
   // global pool + the FC head reading it -> one launch (kernels/misc.hip gap_fc_kernel).  Off: at

@@ -64,9 +64,15 @@ class HipEngine : public Engine {
     max_batch_ = std::max(1, opt.max_batch);
     depth_ = std::max(1, std::min(opt.pipeline_depth, 4));
     // fp32 (the reference's ORT numerics): split hi/lo bf16 operands on the matrix cores
-    plan_ = build_plan(model, max_batch_, opt.branch_streams && opt.exec_streams <= 1, opt.precision == "fp32", opt.bn_on_load,
-                       opt.fuse_pairs, opt.fuse_stem_pool, opt.fuse_gap_fc, opt.fold_layernorm,
-                       opt.ln_stats_epilogue);
+    PlanOptions po;
+    po.side_branches = opt.branch_streams && opt.exec_streams <= 1;
+    po.split = opt.precision == "fp32";
+    po.fuse_pairs = opt.fuse_pairs;
+    po.fuse_stem_pool = opt.fuse_stem_pool;
+    po.fuse_gap_fc = opt.fuse_gap_fc;
+    po.fold_layernorm = opt.fold_layernorm;
+    po.ln_stats_epilogue = opt.ln_stats_epilogue;
+    plan_ = build_plan(model, max_batch_, po);
     sp_ = plan_.split ? 1 : 0;
     while (n_prep_ops_ < plan_.ops.size() && plan_.ops[n_prep_ops_].kind == PlanOp::INPUT_PREP) {
       prep_out_ids_.push_back(plan_.ops[n_prep_ops_].out);
@@ -736,8 +742,8 @@ class HipEngine : public Engine {
         j["vocab"] = emb->gidx;
         static const char* cmp[] = {"==", ">", "<"};
         if (emb->out2 >= 0)  // a key is visible where this holds
-          j["pad_compare"] = std::string(emb->is_max ? "not " : "") + (emb->in_relu ? "trunc(id) " : "id ") + cmp[emb->act] +
-                             " " + std::to_string(emb->clip_lo);
+          j["pad_compare"] = std::string(emb->pad.negated ? "not " : "") + (emb->pad.truncated ? "trunc(id) " : "id ") +
+                             cmp[emb->pad.op] + " " + std::to_string(emb->pad.value);
         else j["pad_compare"] = "none";
       }
     }
@@ -874,9 +880,9 @@ class HipEngine : public Engine {
       if (op.out2 >= 0) {
         bool found = false;
         for (int c = 0; c < op.gidx && !found; ++c) {  // ids near the compare constant first, then 0, 1, ...
-          for (float t : {op.clip_lo + 1.f + c, op.clip_lo - 1.f - c, static_cast<float>(c)}) {
+          for (float t : {op.pad.value + 1.f + c, op.pad.value - 1.f - c, static_cast<float>(c)}) {
             if (t < 0.f || t > static_cast<float>(op.gidx - 1) || t != std::floor(t)) continue;
-            if (kern::token_visible_host(t, op.act, op.clip_lo, op.is_max, op.in_relu)) {
+            if (kern::token_visible_host(t, op.pad.op, op.pad.value, op.pad.negated, op.pad.truncated)) {
               id = t;
               found = true;
               break;
@@ -920,9 +926,6 @@ class HipEngine : public Engine {
     a.counters = counterss_[s % n_exec_];
     a.counters_n = kCounters;
     a.live = slots_[s].d_lens + live_index();
-    a.in_scale = prm_ptr(op.in_scale_off);
-    a.in_shift = prm_ptr(op.in_shift_off);
-    a.in_relu = op.in_relu;
     const float* in3 = op.in3 >= 0 ? static_cast<const float*>(buf_ptr(op.in3, s)) : nullptr;
     a.row_stats = op.in3_parts ? nullptr : in3;
     a.row_parts = op.in3_parts ? in3 : nullptr;
@@ -1151,7 +1154,7 @@ class HipEngine : public Engine {
         // 1024 blocks splitting the tiles x K-steps evenly (ConvArgs::sk) -- for grids whose tile
         // count lands just past a multiple of the CU count (ResNet50 stage-3 reduce at B = 24: 296
         // tiles = two tiles on 40 CUs, one on the rest)
-        if (opt_.tune_streamk && base.N % 8 == 0 && !base.in_scale && !base.row_parts && !base.stats_out)
+        if (opt_.tune_streamk && base.N % 8 == 0 && !base.row_parts && !base.stats_out)
           for (int tile = 0; tile < kern::NUM_CFGS; ++tile) {
             const int v = tile / kern::NUM_TILES;
             if (v != 1 && v != 5) continue;  // 2-stage ring and 1-stage loop
@@ -1504,7 +1507,7 @@ class HipEngine : public Engine {
                               static_cast<const uint16_t*>(buf(op.in3)) + op.col[2], static_cast<uint16_t*>(buf(op.out)),
                               B, op.S, op.nh, op.hd, op.ld[0], op.ld[1], op.ld[2], op.C, op.fscale, st, sp_,
                               op.bias_heads ? prm(op.bias_off) : nullptr, op.bias_heads,
-                              op.bias_heads || op.key_mask ? (op.S + 31) / 32 * 32 : 0, op.causal,
+                              op.bias_heads || op.key_mask ? kern::key_pitch(op.S) : 0, op.causal,
                               op.key_mask ? static_cast<const float*>(buf(op.in4)) : nullptr,
                               op.key_mask ? static_cast<const int*>(buf(op.in5)) : nullptr);
           break;
@@ -1512,7 +1515,8 @@ class HipEngine : public Engine {
           e = kern::embed_tokens(static_cast<const float*>(buf(op.in)), prm(op.w_off), op.C, prm(op.shift_off),
                                  prm(op.bias_off), static_cast<uint16_t*>(buf(op.out)), B, op.S, op.gidx, op.C, st, sp_,
                                  static_cast<float*>(buf(op.out2)), static_cast<int*>(buf(op.out3)),
-                                 op.out2 >= 0 ? (op.S + 31) / 32 * 32 : 0, op.act, op.clip_lo, op.is_max, op.in_relu);
+                                 op.out2 >= 0 ? kern::key_pitch(op.S) : 0, op.pad.op, op.pad.value, op.pad.negated,
+                                 op.pad.truncated);
           break;
         case PlanOp::POOL_TOKENS:
           e = kern::pool_tokens(static_cast<const uint16_t*>(buf(op.in)),
@@ -1520,7 +1524,7 @@ class HipEngine : public Engine {
                                 op.out_f32 != -1 ? static_cast<float*>(buf(op.out_f32)) : nullptr, B, op.S, op.C, op.Cp,
                                 op.key_mask ? static_cast<const float*>(buf(op.in4)) : nullptr,
                                 op.key_mask ? static_cast<const int*>(buf(op.in5)) : nullptr,
-                                op.key_mask ? (op.S + 31) / 32 * 32 : 0, op.clip_lo, op.act, op.eps, st, live, sp_,
+                                op.key_mask ? kern::key_pitch(op.S) : 0, op.count_min, op.normalize, op.eps, st, live, sp_,
                                 side ? ws_side_ : wss_[s % n_exec_], ws_bytes_, side ? counters_side_ : counterss_[s % n_exec_],
                                 kCounters);
           break;
@@ -1633,7 +1637,7 @@ class HipEngine : public Engine {
       }
       if (op.kind == PlanOp::POOL_TOKENS) {
         o["masked"] = op.key_mask != 0;
-        o["normalize"] = op.act != 0;
+        o["normalize"] = op.normalize;
       }
       total += us[i];
       ops.push_back(o);

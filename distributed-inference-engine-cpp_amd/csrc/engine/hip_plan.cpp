@@ -1,5 +1,7 @@
 #include "hip_plan.h"
 
+#include "plan_passes.h"
+
 #include <algorithm>
 #include <array>
 #include <climits>
@@ -16,25 +18,11 @@ using onnx::Node;
 
 namespace {
 
-constexpr int kBufGraphIn = -2;
-constexpr int kBufGraphOut = -3;
-
-uint16_t to_bf16(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7F800000u) == 0x7F800000u) return static_cast<uint16_t>(u >> 16);  // inf/nan
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return static_cast<uint16_t>(u >> 16);
-}
-
-size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-float from_bf16(uint16_t h) {
-  const uint32_t u = static_cast<uint32_t>(h) << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
+using passes::from_bf16;
+using passes::kBufGraphIn;
+using passes::kBufGraphOut;
+using passes::round_up;
+using passes::to_bf16;
 
 constexpr int64_t kBatchDim = INT64_MIN;  // symbolic batch size inside SHAPE values
 
@@ -78,12 +66,12 @@ struct Val {
   float scale = 1.f;
   int mask = -1;  // ATTN stage 0/1/2: index of the folded bias / mask table (Planner::masks_), -1 = none
   bool kmask = false;  // ATTN: the scores carry the request's key mask (PlanOp::key_mask)
-  // TOKEN_IDS: kv_trunc = behind a Cast to an integer type.  KEYVIS: the value is true (additive
-  // form: masked, i.e. <= -1e4) where ((kv_trunc ? trunc(id) : id) OP kv_c) != kv_neg, OP = kv_op
-  // (0 Equal, 1 Greater, 2 Less); kv_rank = 2 [N, S], 3 [N, 1, S], 4 [N, 1, 1, S]
-  int kv_op = 0, kv_rank = 2;
-  float kv_c = 0.f;
-  bool kv_neg = false, kv_trunc = false, kv_add = false;
+  // TOKEN_IDS: pad.truncated = behind a Cast to an integer type.  KEYVIS: the value is true (additive
+  // form, kv_add: masked, i.e. <= -1e4) where the test `pad` holds; kv_rank = 2 [N, S], 3 [N, 1, S],
+  // 4 [N, 1, 1, S]
+  PadTest pad;
+  int kv_rank = 2;
+  bool kv_add = false;
   // KEYVIS for pooling: kv_last = unsqueezed at the LAST axis, [N, S, 1] (kv_rank 3), kv_D > 0 = then
   // expanded to [N, S, kv_D].  POOLV keeps the mask's fields; pool_c = stage 2: the count's lower bound
   bool kv_last = false;
@@ -103,12 +91,8 @@ int round8(int c) { return (c + 7) / 8 * 8; }
 
 class Planner {
  public:
-  Planner(const onnx::Model& m, int max_batch, bool side_branches, bool split, bool bn_on_load, bool fuse_pairs = true,
-          bool fuse_stem_pool = true, bool fuse_gap_fc = false, bool fold_layernorm = true,
-          bool ln_stats_epilogue = true)
-      : m_(m), max_batch_(max_batch), side_branches_(side_branches), split_(split), bn_on_load_(bn_on_load),
-        fuse_pairs_(fuse_pairs), fuse_stem_pool_(fuse_stem_pool), fuse_gap_fc_(fuse_gap_fc),
-        fold_layernorm_(fold_layernorm), ln_stats_epilogue_(ln_stats_epilogue) {}
+  Planner(const onnx::Model& m, int max_batch, const PlanOptions& opt)
+      : m_(m), max_batch_(max_batch), opt_(opt) {}
 
   // Every node is tried; a node that cannot be lowered is recorded (with its error) and its
   // outputs become UNKNOWN, so the walk goes on and the report lists every unsupported node.
@@ -121,7 +105,7 @@ class Planner {
     for (auto& o : m_.outputs) graph_outputs_.insert(o.name);
     for (size_t i = 0; i < m_.nodes.size(); ++i)
       for (auto& o : m_.nodes[i].outputs) producer_[o] = static_cast<int>(i);
-    plan_.split = split_;
+    plan_.split = opt_.split;
     define_graph_input();
 
     done_.assign(m_.nodes.size(), false);
@@ -153,17 +137,16 @@ class Planner {
     }
     if (!report_.supported) throw PlanUnsupported("HIP engine cannot lower this graph:\n" + report_.text());
     finalize_output();
-    fuse_pool_affine();
-    if (fuse_stem_pool_) fuse_stem_pool();
-    if (fuse_pairs_) fuse_conv_pairs();
-    if (fuse_gap_fc_) fuse_gap_fc();
+    passes::fuse_pool_affine(plan_);
+    if (opt_.fuse_stem_pool) passes::fuse_stem_pool(plan_);
+    if (opt_.fuse_pairs) passes::fuse_conv_pairs(plan_);
+    if (opt_.fuse_gap_fc) passes::fuse_gap_fc(plan_, max_batch_);
     // fp32 (split) mode only: in bf16 the weights re-rounded with gamma folded in and the mean
     // subtracted after a bf16-input GEMM cost ViT-B/16 ~3 % of its rel-L2 budget
-    if (fold_layernorm_ && split_) fold_layernorm();
-    if (fold_layernorm_ && split_ && ln_stats_epilogue_) stats_from_producer();
-    if (bn_on_load_ && !split_) preact_on_load();  // measured slower (profiles/r1_preact_on_load.md)
-    if (side_branches_) mark_side_branches();
-    assign_arena();
+    if (opt_.fold_layernorm && opt_.split) passes::fold_layernorm(plan_);
+    if (opt_.fold_layernorm && opt_.split && opt_.ln_stats_epilogue) passes::stats_from_producer(plan_);
+    if (opt_.side_branches) passes::mark_side_branches(plan_);
+    passes::assign_arena(plan_, max_batch_);
     return std::move(plan_);
   }
 
@@ -195,39 +178,23 @@ class Planner {
     auto it = consumers_.find(name);
     return it == consumers_.end() ? std::vector<int>{} : it->second;
   }
-  // An activation buffer of `bytes_per_sample` bf16 bytes (fp32 mode: hi and lo planes, twice that).
-  int new_buf(size_t bytes_per_sample) {
-    PlanBuf b;
-    b.bytes_per_sample = bytes_per_sample * (split_ ? 2 : 1);
-    plan_.bufs.push_back(b);
-    return static_cast<int>(plan_.bufs.size()) - 1;
-  }
-  size_t push_f32(const std::vector<float>& v) {
-    size_t off = round_up(plan_.params.size(), 256);
-    plan_.params.resize(off + round_up(v.size(), 128) * 4, 0);
-    std::memcpy(plan_.params.data() + off, v.data(), v.size() * 4);
-    return off;
-  }
-  size_t push_bf16(const std::vector<uint16_t>& v) {
-    size_t off = round_up(plan_.params.size(), 256);
-    plan_.params.resize(off + v.size() * 2);
-    std::memcpy(plan_.params.data() + off, v.data(), v.size() * 2);
-    return off;
-  }
+  int new_buf(size_t bytes_per_sample) { return passes::new_buf(plan_, bytes_per_sample); }
+  size_t push_f32(const std::vector<float>& v) { return passes::push_f32(plan_, v); }
+  size_t push_bf16(const std::vector<uint16_t>& v) { return passes::push_bf16(plan_, v); }
   // GEMM weights given in fp32: bf16, or (fp32 mode) the hi plane followed by the lo plane
   // (lo = bf16(w - hi)); `wplane` receives the plane distance in elements (0 when not split).
   size_t push_weights(const std::vector<float>& w, long long& wplane) {
-    std::vector<uint16_t> q(w.size() * (split_ ? 2 : 1));
+    std::vector<uint16_t> q(w.size() * (opt_.split ? 2 : 1));
     for (size_t i = 0; i < w.size(); ++i) {
       q[i] = to_bf16(w[i]);
-      if (split_) {
+      if (opt_.split) {
         uint32_t u = static_cast<uint32_t>(q[i]) << 16;
         float hi;
         std::memcpy(&hi, &u, 4);
         q[w.size() + i] = to_bf16(w[i] - hi);
       }
     }
-    wplane = split_ ? static_cast<long long>(w.size()) : 0;
+    wplane = opt_.split ? static_cast<long long>(w.size()) : 0;
     return push_bf16(q);
   }
   void add_op(PlanOp op) { plan_.ops.push_back(std::move(op)); }
@@ -253,7 +220,7 @@ class Planner {
       in.kind = Val::TOKEN_IDS;
       in.H = static_cast<int>(vi.dims[1]);
       in.buf = kBufGraphIn;
-      in.kv_trunc = vi.elem_type == onnx::INT64 || vi.elem_type == onnx::INT32;
+      in.pad.truncated = vi.elem_type == onnx::INT64 || vi.elem_type == onnx::INT32;
       define(vi.name, in);
       plan_.input_shape = {1, in.H};
       plan_.input_numel = static_cast<size_t>(in.H);
@@ -587,7 +554,7 @@ class Planner {
       wp.swap(ws);
     }
     p.w_off = push_weights(wp, p.conv.wplane);
-    p.conv.split = split_;
+    p.conv.split = opt_.split;
     p.bias_off = push_f32(shift);
     auto& a = p.conv;
     a.H = x.H;
@@ -821,7 +788,7 @@ class Planner {
     p.name = group.size() > 1 ? n.name + "+qkv" : n.name;
     p.in = x.buf;
     p.w_off = push_weights(wp, p.conv.wplane);
-    p.conv.split = split_;
+    p.conv.split = opt_.split;
     auto& a = p.conv;
     a.H = a.Ho = rows;
     a.Cin = Ks;
@@ -881,6 +848,13 @@ class Planner {
   }
 
   // ---- transformer views / ops --------------------------------------------------------------------
+  // The axes of a Reduce* / Unsqueeze node: the attribute, or (opset 13+) input 1.  False when there
+  // are none or they are not known.
+  bool node_axes(const Node& n, std::vector<int64_t>& ax) const {
+    ax = n.get_ints("axes");
+    if (ax.empty() && n.inputs.size() > 1 && !n.in(1).empty()) return ints_of(n.in(1), ax) && !ax.empty();
+    return !ax.empty();
+  }
   bool ints_of(const std::string& nm, std::vector<int64_t>& out) const {
     auto it = vid_.find(nm);
     if (it != vid_.end() && vals_[it->second].kind == Val::SHAPE) {
@@ -1017,7 +991,7 @@ class Planner {
         const int to = static_cast<int>(n.get_int("to", onnx::FLOAT));
         if (to != onnx::INT64 && to != onnx::INT32) throw std::runtime_error(who + "token ids cast only to INT64 / INT32");
         Val o = *ids;
-        o.kv_trunc = true;
+        o.pad.truncated = true;
         define(n.outputs[0], o);
         return;
       }
@@ -1031,9 +1005,9 @@ class Planner {
         Val o;
         o.kind = Val::KEYVIS;
         o.H = ids->H;
-        o.kv_op = op == "Equal" ? 0 : (op == "Greater") == (side == 0) ? 1 : 2;  // c > ids = ids < c
-        o.kv_c = c;
-        o.kv_trunc = ids->kv_trunc;
+        o.pad.op = op == "Equal" ? 0 : (op == "Greater") == (side == 0) ? 1 : 2;  // c > ids = ids < c
+        o.pad.value = c;
+        o.pad.truncated = ids->pad.truncated;
         define(n.outputs[0], o);
         return;
       }
@@ -1045,12 +1019,7 @@ class Planner {
       for (int side = 1; side <= 2 && m; ++side) {
         const Val* x = val_if(n.in(side), Val::ATTN);
         if (!x || x->stage != 0) continue;
-        float f = 0.f;
-        if (!scalar_init(n.in(3 - side), f))
-          throw std::runtime_error("Where " + n.name + ": on attention scores the other branch must be a scalar initializer");
-        if (!(f <= -1e4f))
-          throw std::runtime_error("Where " + n.name + ": fill " + std::to_string(f) + " is not a mask (only fills <= -1e4 or "
-                                   "-inf fold into the attention kernel as -inf); a finite fill above -1e4 is not supported");
+        check_score_fill(n, n.in(3 - side));
         if (m->kv_add) throw std::runtime_error(who + "the condition must be a boolean key mask");
         return define_key_masked(n, *x, *m, side == 1);
       }
@@ -1068,13 +1037,13 @@ class Planner {
     const Val* m = n.inputs.empty() ? nullptr : val_if(n.in(0), Val::KEYVIS);
     if (m && !m->kv_add && (op == "Not" || op == "Cast" || op == "Identity")) {
       Val o = *m;
-      if (op == "Not") o.kv_neg = !o.kv_neg;
+      if (op == "Not") o.pad.negated = !o.pad.negated;
       define(n.outputs[0], o);
       return;
     }
     if (m && op == "Unsqueeze") {
-      std::vector<int64_t> axes = n.get_ints("axes");
-      if (axes.empty() && n.inputs.size() > 1) ints_of(n.in(1), axes);
+      std::vector<int64_t> axes;
+      node_axes(n, axes);
       Val o = *m;
       o.kv_rank = m->kv_rank + static_cast<int>(axes.size());
       bool ok = !axes.empty() && o.kv_rank <= 4;
@@ -1099,7 +1068,7 @@ class Planner {
     if (op == "Sub" && n.inputs.size() == 2 && scalar_is(n.in(0), 1.f)) {  // 1 - m
       if (const Val* s = val_if(n.in(1), Val::KEYVIS); s && !s->kv_add) {
         Val o = *s;
-        o.kv_neg = !o.kv_neg;
+        o.pad.negated = !o.pad.negated;
         define(n.outputs[0], o);
         return;
       }
@@ -1202,21 +1171,18 @@ class Planner {
   void bind_key_test(const std::string& who, const Val& m, bool vis_when_true) {
     if (key_op_ < 0)
       throw std::runtime_error(who + "a key mask needs the token embedding (EMBED_TOKENS writes the key data) lowered first");
-    // visible = ((trunc ? trunc(id) : id) OP c) != neg
-    const int neg = (m.kv_neg != !vis_when_true) ? 1 : 0;
+    PadTest visible = m.pad;  // m's value is true where m.pad holds
+    visible.negated = m.pad.negated != !vis_when_true;
     PlanOp& e = plan_.ops[key_op_];
     if (!key_test_set_) {
       key_test_set_ = true;
-      e.act = m.kv_op;
-      e.clip_lo = m.kv_c;
-      e.is_max = neg;
-      e.in_relu = m.kv_trunc ? 1 : 0;
-      const int Sp = (m.H + 31) / 32 * 32;
+      e.pad = visible;
+      const int Sp = kern::key_pitch(m.H);
       e.out2 = new_buf(static_cast<size_t>(Sp) * 4);  // kvis: fp32 [Sp] per sample
       e.out3 = new_buf(16);                           // kend: one int per sample
       plan_.bufs[e.out2].bytes_per_sample = static_cast<size_t>(Sp) * 4;  // (fp32 in both precisions)
       plan_.bufs[e.out3].bytes_per_sample = 4;
-    } else if (e.act != m.kv_op || e.clip_lo != m.kv_c || e.is_max != neg || e.in_relu != (m.kv_trunc ? 1 : 0)) {
+    } else if (!(e.pad == visible)) {
       throw std::runtime_error(who + "a second, different pad test (one key mask per model: every attention shares the key data)");
     }
   }
@@ -1228,11 +1194,6 @@ class Planner {
   // reading the key data of the plan's EMBED_TOKENS op.  An L2 normalisation that is the pooled
   // vector's only reader sets the op's normalize flag; on any other rank-2 rows it is a POOL_TOKENS op
   // with S = 1.
-  bool reduce_axes(const Node& n, std::vector<int64_t>& ax) const {
-    ax = n.get_ints("axes");
-    if (ax.empty() && n.inputs.size() > 1 && !n.in(1).empty()) return ints_of(n.in(1), ax) && !ax.empty();
-    return !ax.empty();
-  }
 
   // `name` is written by ReduceSum(Mul(., .)): the shape of a masked sum (whether the Mul has a key
   // mask operand is that Mul's business)
@@ -1250,8 +1211,8 @@ class Planner {
     auto fail = [&](const std::string& why) { throw std::runtime_error(who + why); };
     const Val* m = n.inputs.empty() ? nullptr : val_if(n.in(0), Val::KEYVIS);
     if (m && op == "Unsqueeze" && m->kv_rank == 2 && !m->kv_add) {  // [N, S] -> [N, S, 1]
-      std::vector<int64_t> axes = n.get_ints("axes");
-      if (axes.empty() && n.inputs.size() > 1) ints_of(n.in(1), axes);
+      std::vector<int64_t> axes;
+      node_axes(n, axes);
       if (axes.size() != 1 || !(axes[0] == -1 || axes[0] == 2)) return false;  // towards [N, 1, 1, S]: lower_token_node
       Val o = *m;
       o.kv_rank = 3;
@@ -1285,7 +1246,7 @@ class Planner {
         if (s->kv_D && s->kv_D != x->logical() && s->kv_D != x->C) fail("the expanded key mask's width is not the rows'");
         const int r = sole_consumer(n.outputs[0]);
         std::vector<int64_t> ax;
-        if (r < 0 || m_.nodes[r].op_type != "ReduceSum" || !reduce_axes(m_.nodes[r], ax) || ax.size() != 1 ||
+        if (r < 0 || m_.nodes[r].op_type != "ReduceSum" || !node_axes(m_.nodes[r], ax) || ax.size() != 1 ||
             !(ax[0] == 1 || ax[0] == -2) || m_.nodes[r].get_int("keepdims", 1) != 0)
           fail("rows times a key mask feed only ReduceSum(axis 1, keepdims 0), the masked sum over the tokens");
         Val o = *s;
@@ -1300,7 +1261,7 @@ class Planner {
       }
     if (op == "ReduceSum" && !n.inputs.empty()) {
       std::vector<int64_t> ax;
-      reduce_axes(n, ax);
+      node_axes(n, ax);
       const bool keep = n.get_int("keepdims", 1) != 0;
       if (const Val* r = val_if(n.in(0), Val::POOLV)) {  // the masked sum (axes checked by the Mul)
         if (r->stage != 0) fail("only rows times a key mask are summed over the tokens");
@@ -1368,7 +1329,7 @@ class Planner {
       if (a || b) {
         if (!a || !b || a->stage != 1 || b->stage != 2)
           fail("masked mean pooling divides the masked sum over the tokens by the count of visible tokens, nothing else");
-        if (a->kv_op != b->kv_op || a->kv_c != b->kv_c || a->kv_neg != b->kv_neg || a->kv_trunc != b->kv_trunc)
+        if (!(a->pad == b->pad))
           fail("the count is not over the visibility value of the masked sum (different pad tests)");
         if (b->kv_D && b->kv_D != a->logical() && b->kv_D != a->C) fail("the count's width is not the masked sum's");
         const Val rows = *a, vis = *a;
@@ -1391,7 +1352,7 @@ class Planner {
     const Node& r = m_.nodes[ridx];
     const std::string& x = r.in(0);
     std::vector<int64_t> ax;
-    if (!reduce_axes(r, ax) || ax.size() != 1 || !(ax[0] == -1 || ax[0] == rank - 1) || r.get_int("keepdims", 1) != 1) {
+    if (!node_axes(r, ax) || ax.size() != 1 || !(ax[0] == -1 || ax[0] == rank - 1) || r.get_int("keepdims", 1) != 1) {
       why = "the norm is taken over the last axis with keepdims 1";
       return false;
     }
@@ -1508,7 +1469,7 @@ class Planner {
     p.S = S;
     p.C = x.C;
     p.Cp = x.logical();
-    p.clip_lo = clip_min;
+    p.count_min = clip_min;
     if (vis) {
       bind_key_test(n.op_type + " " + n.name + ": ", *vis, true);  // the mask multiplies: true = visible
       p.key_mask = 1;
@@ -1523,7 +1484,7 @@ class Planner {
       p.name += "+" + m_.nodes[used[0]].name;
       out_name = nout;
     }
-    p.act = normalize ? 1 : 0;
+    p.normalize = normalize;
     p.eps = normalize ? eps : 0.f;
     p.flops_per_sample = static_cast<double>(S) * p.Cp;
     Val o;
@@ -1702,7 +1663,7 @@ class Planner {
       }
       const bool zero = std::all_of(t.t.begin(), t.t.end(), [](float e) { return e == 0.f; });
       if (!zero) {  // [heads][S][Sp], rows padded to a multiple of 32, in the kernel's exp2 units
-        const int Sp = (S + 31) / 32 * 32;
+        const int Sp = kern::key_pitch(S);
         std::vector<float> tab(static_cast<size_t>(t.heads) * S * Sp, 0.f);
         for (size_t row = 0; row < static_cast<size_t>(t.heads) * S; ++row)
           for (int j = 0; j < S; ++j) tab[row * Sp + j] = t.t[row * S + j] * 1.4426950408889634f;
@@ -1819,7 +1780,7 @@ class Planner {
           q.C = static_cast<int>(D);
           q.Cp = round8(static_cast<int>(D));
           q.rows_per_sample = S;
-          plan_.bufs[q.out].bytes_per_sample = static_cast<size_t>(S) * q.Cp * 2 * (split_ ? 2 : 1);
+          plan_.bufs[q.out].bytes_per_sample = static_cast<size_t>(S) * q.Cp * 2 * (opt_.split ? 2 : 1);
           Val o = x;
           o.H = static_cast<int>(S);
           o.W = 1;
@@ -2278,8 +2239,8 @@ class Planner {
   bool lower_spatial_reduce(int idx, int mode) {
     const Node& n = m_.nodes[idx];
     const Val x = materialize_in(n.in(0), n);
-    std::vector<int64_t> ax = n.get_ints("axes");
-    if (ax.empty() && n.inputs.size() > 1 && !n.in(1).empty()) ints_of(n.in(1), ax);
+    std::vector<int64_t> ax;
+    node_axes(n, ax);
     std::sort(ax.begin(), ax.end());
     const bool keep = n.get_int("keepdims", 1) != 0;
     const bool spatial = x.kind == Val::NHWC && (ax == std::vector<int64_t>{2, 3} || ax == std::vector<int64_t>{-2, -1});
@@ -2463,6 +2424,15 @@ class Planner {
     v = it->second.f.empty() ? static_cast<float>(it->second.i.at(0)) : it->second.f[0];
     return true;
   }
+  // The other branch `fill` of the Where `n` on attention scores: a scalar initializer <= -1e4.
+  void check_score_fill(const Node& n, const std::string& fill) const {
+    float f = 0.f;
+    if (!scalar_init(fill, f))
+      throw std::runtime_error("Where " + n.name + ": on attention scores the other branch must be a scalar initializer");
+    if (!(f <= -1e4f))
+      throw std::runtime_error("Where " + n.name + ": fill " + std::to_string(f) + " is not a mask (only fills <= -1e4 or "
+                               "-inf fold into the attention kernel as -inf); a finite fill above -1e4 is not supported");
+  }
 
   // Comparisons (bool results are stored as 1 / 0 activations): two activations -> a binary op,
   // an activation and a scalar constant -> a unary code (the constant on the left mirrors the test).
@@ -2492,12 +2462,7 @@ class Planner {
       auto it = vid_.find(n.in(side));
       if (it == vid_.end() || vals_[it->second].kind != Val::ATTN || vals_[it->second].stage != 0) continue;
       const Val x = vals_[it->second];
-      float f = 0.f;
-      if (!scalar_init(n.in(3 - side), f))
-        throw std::runtime_error("Where " + n.name + ": on attention scores the other branch must be a scalar initializer");
-      if (!(f <= -1e4f))
-        throw std::runtime_error("Where " + n.name + ": fill " + std::to_string(f) + " is not a mask (only fills <= -1e4 or "
-                                 "-inf fold into the attention kernel as -inf); a finite fill above -1e4 is not supported");
+      check_score_fill(n, n.in(3 - side));
       return lower_attn_mask(n, x, n.in(0), side == 1 ? 1 : 2);
     }
     const Val c = materialize_in(n.in(0), n);
@@ -3106,460 +3071,9 @@ class Planner {
     for (auto dim : plan_.output_shape) plan_.output_numel *= static_cast<size_t>(dim);
   }
 
-  // Pool -> BN(+ReLU) where the pooled value has no other reader (ResNet-v2: the stem's max pool
-  // feeds only stage 1's pre-activation BN, the first unit having a projection shortcut): the pool
-  // kernel applies the per-channel affine and activation before its single store.
-  void fuse_pool_affine() {
-    std::vector<int> readers(plan_.bufs.size(), 0);
-    for (const PlanOp& p : plan_.ops)
-      for (int b : {p.in, p.in2, p.in3})
-        if (b >= 0) readers[b]++;
-    std::vector<PlanOp> out;
-    out.reserve(plan_.ops.size());
-    for (size_t i = 0; i < plan_.ops.size(); ++i) {
-      PlanOp& p = plan_.ops[i];
-      if (p.kind == PlanOp::AFFINE && p.in2 < 0 && p.in >= 0 && readers[p.in] == 1 && !out.empty() &&
-          out.back().kind == PlanOp::POOL && out.back().out == p.in && out.back().scale_off == SIZE_MAX &&
-          out.back().act == 0 && p.rows_per_sample == static_cast<long long>(out.back().Ho) * out.back().Wo) {
-        PlanOp& pool = out.back();
-        pool.scale_off = p.scale_off;
-        pool.shift_off = p.shift_off;
-        pool.act = p.act;
-        pool.out = p.out;
-        pool.name += "+" + p.name;
-        continue;
-      }
-      out.push_back(std::move(p));
-    }
-    plan_.ops = std::move(out);
-  }
-
-  // Stem -> 3x3/2 max pool (pad 1) [-> the pooled value's BN/ReLU, fuse_pool_affine] where the stem
-  // map has no other reader: one STEM op with is_max = 1 (kernels/stem.hip stem_pool_nchw_kernel);
-  // the stem map is never stored.  Ho/Wo become the pooled size, s2_off/b2_off/act the pool's affine.
-  void fuse_stem_pool() {
-    std::vector<int> readers(plan_.bufs.size(), 0);
-    for (const PlanOp& p : plan_.ops)
-      for (int b : {p.in, p.in2, p.in3})
-        if (b >= 0) readers[b]++;
-    std::vector<PlanOp> out;
-    out.reserve(plan_.ops.size());
-    for (size_t i = 0; i < plan_.ops.size(); ++i) {
-      PlanOp& p = plan_.ops[i];
-      if (p.kind == PlanOp::POOL && p.is_max && p.kh == 3 && p.kw == 3 && p.sh == 2 && p.sw == 2 && p.ph == 1 &&
-          p.pw == 1 && p.act <= 1 && p.C == 64 && p.in >= 0 && readers[p.in] == 1 && !out.empty()) {
-        PlanOp& s = out.back();
-        const auto& c = s.conv;
-        if (s.kind == PlanOp::STEM && s.in == kBufGraphIn && !s.is_max && s.out == p.in && c.Ho == p.H && c.Wo == p.W &&
-            kern::stem_pool_supported(c.H, c.W, c.Ho, c.Wo, p.Ho, p.Wo, split_)) {
-          permute_weight_rows(s.w_off, 64, 224, c.wplane);
-          s.is_max = 1;
-          s.Ho = p.Ho;
-          s.Wo = p.Wo;
-          s.s2_off = p.scale_off;
-          s.b2_off = p.shift_off;
-          s.act = p.act;
-          s.out = p.out;
-          s.name += "+" + p.name;
-          continue;
-        }
-      }
-      out.push_back(std::move(p));
-    }
-    plan_.ops = std::move(out);
-  }
-
-  // Global pool -> the FC head (Gemm / 1x1 conv over the pooled [C] vector) that is its ONLY reader,
-  // with an fp32 output (a buffer or the graph output, directly or through a BF16_TO_F32 op) and no
-  // residual / second output: one GAP_FC op at the pool's position
-  // (kernels/misc.hip gap_fc_kernel); the pooled vector is never stored.
-  void fuse_gap_fc() {
-    std::vector<int> readers(plan_.bufs.size(), 0), reader_op(plan_.bufs.size(), -1);
-    const int nops = static_cast<int>(plan_.ops.size());
-    for (int i = 0; i < nops; ++i)
-      for (int b : {plan_.ops[i].in, plan_.ops[i].in2, plan_.ops[i].in3})
-        if (b >= 0) {
-          readers[b]++;
-          reader_op[b] = i;
-        }
-    std::vector<bool> drop(nops, false);
-    for (int i = 0; i < nops; ++i) {
-      PlanOp& p = plan_.ops[i];
-      if (p.kind != PlanOp::GAP || p.out < 0 || p.out2 >= 0 || p.out_f32 != -1 || p.join >= 0 || p.in < 0 ||
-          readers[p.out] != 1)
-        continue;
-      const int j = reader_op[p.out];
-      if (j <= i || drop[j]) continue;
-      const PlanOp& q = plan_.ops[j];
-      const kern::ConvArgs& c = q.conv;
-      if (q.kind != PlanOp::CONV || q.in != p.out || q.in2 >= 0 || q.in3 >= 0 || q.out2 >= 0 || q.join >= 0 ||
-          c.relu > 1 || q.in_scale_off != SIZE_MAX || c.KH != 1 || c.KW != 1 || c.H != 1 || c.W != 1 ||
-          c.Cin != p.C || c.K != p.C)
-        continue;
-      // the f32 logits come from the conv itself, or (N % 8 != 0) from the BF16_TO_F32 op that is
-      // the only reader of its bf16 output -- the fused op writes them directly, in fp32
-      int conv_out = -1, nout = c.N, k = -1;
-      if (q.out_f32 != -1 && q.out < 0) {
-        conv_out = q.out_f32;
-      } else if (q.out_f32 == -1 && q.out >= 0 && readers[q.out] == 1) {
-        k = reader_op[q.out];
-        const PlanOp& r = plan_.ops[k];
-        if (k <= j || drop[k] || r.kind != PlanOp::BF16_TO_F32 || r.in != q.out || r.out_f32 == -1 || r.join >= 0 ||
-            (r.ld_store > 0 && r.rows_per_sample != 1) || r.C > c.N)
-          continue;
-        conv_out = r.out_f32;
-        nout = r.C;
-      } else {
-        continue;
-      }
-      if (!kern::gap_fc_slice(p.C, max_batch_, nout, kern::kSplitKWorkspaceBytes)) continue;
-      p.kind = PlanOp::GAP_FC;
-      p.name += "+" + q.name;
-      p.conv = c;
-      p.Cp = nout;  // logits per sample (= the f32 row pitch)
-      p.w_off = q.w_off;
-      p.bias_off = q.bias_off;
-      p.act = c.relu;
-      p.out = -1;  // the pooled buffer is dropped (no op references it any more)
-      p.out_f32 = conv_out;
-      p.flops_per_sample += q.flops_per_sample;
-      drop[j] = true;
-      if (k >= 0) drop[k] = true;
-    }
-    std::vector<PlanOp> out;
-    out.reserve(plan_.ops.size());
-    for (int i = 0; i < nops; ++i)
-      if (!drop[i]) out.push_back(std::move(plan_.ops[i]));
-    plan_.ops = std::move(out);
-  }
-
-  // LayerNorm -> GEMMs (ViT / BERT pre-norm blocks: the norm feeds the QKV or the first MLP GEMM
-  // only).  LN(x) W + b = rstd (x (gamma W) - mean colsum(gamma W)) + (beta W + b) per row, so the
-  // GEMMs read x itself with gamma folded into their weights, beta into their bias, and apply the
-  // per-row (mean, rstd) in the epilogue (ConvArgs::row_stats); the LayerNorm only computes the
-  // statistics -- the normalised rows are never written or read.  Exact in real arithmetic; in
-  // fp32 the error grows with |mean| / std of a row (ViT residual rows: mean ~ 0).
-  double weight_at(size_t w_off, long long plane, int kpad, int n, int k) const {
-    const uint16_t* w = reinterpret_cast<const uint16_t*>(plan_.params.data() + w_off);
-    const size_t i = static_cast<size_t>(n) * kpad + k;
-    double v = from_bf16(w[i]);
-    if (plane > 0) v += from_bf16(w[i + plane]);
-    return v;
-  }
-  void set_weight(size_t w_off, long long plane, int kpad, int n, int k, float v) {
-    uint16_t* w = reinterpret_cast<uint16_t*>(plan_.params.data() + w_off);
-    const size_t i = static_cast<size_t>(n) * kpad + k;
-    const uint16_t hi = to_bf16(v);
-    w[i] = hi;
-    if (plane > 0) w[i + plane] = to_bf16(v - static_cast<float>(from_bf16(hi)));
-  }
-  void fold_layernorm() {
-    const int nops = static_cast<int>(plan_.ops.size());
-    std::vector<std::vector<int>> readers(plan_.bufs.size());
-    for (int i = 0; i < nops; ++i)
-      for (int b : {plan_.ops[i].in, plan_.ops[i].in2, plan_.ops[i].in3})
-        if (b >= 0) readers[b].push_back(i);
-    for (int i = 0; i < nops; ++i) {
-      PlanOp& p = plan_.ops[i];
-      if (p.kind != PlanOp::LAYERNORM || p.stats_only || p.out < 0 || p.in < 0 || p.C != p.Cp || p.join >= 0 ||
-          readers[p.out].empty())
-        continue;
-      bool ok = true;
-      for (int j : readers[p.out]) {
-        const PlanOp& q = plan_.ops[j];
-        const kern::ConvArgs& c = q.conv;
-        ok = ok && j > i && q.kind == PlanOp::CONV && q.in == p.out && q.in2 != p.out && q.in3 < 0 && q.join < 0 &&
-             q.in_scale_off == SIZE_MAX && c.KH == 1 && c.KW == 1 && c.stride == 1 && c.pad_h == 0 && c.pad_w == 0 &&
-             c.K == p.C && c.Cin == p.C && c.Kpad == c.K && c.Ho * c.Wo == p.rows_per_sample;
-      }
-      if (!ok) continue;
-      const float* gamma = reinterpret_cast<const float*>(plan_.params.data() + p.scale_off);
-      const float* beta = reinterpret_cast<const float*>(plan_.params.data() + p.shift_off);
-      const std::vector<float> g(gamma, gamma + p.C), be(beta, beta + p.C);
-      const int stats = new_buf(static_cast<size_t>(p.rows_per_sample) * 2 * 4);
-      for (int j : readers[p.out]) {
-        PlanOp& q = plan_.ops[j];
-        const kern::ConvArgs& c = q.conv;
-        const int Npad = static_cast<int>(round_up(c.N, 128));
-        std::vector<float> bias(Npad, 0.f), colsum(round_up(c.N, 8), 0.f);
-        if (q.bias_off != SIZE_MAX) {
-          const float* b0 = reinterpret_cast<const float*>(plan_.params.data() + q.bias_off);
-          std::copy(b0, b0 + c.N, bias.begin());
-        }
-        for (int n = 0; n < c.N; ++n) {
-          double bsum = bias[n], csum = 0.0;
-          for (int k = 0; k < c.K; ++k) {
-            const double w = weight_at(q.w_off, c.wplane, c.Kpad, n, k);
-            bsum += static_cast<double>(be[k]) * w;
-            set_weight(q.w_off, c.wplane, c.Kpad, n, k, static_cast<float>(w * g[k]));
-            csum += weight_at(q.w_off, c.wplane, c.Kpad, n, k);  // what the GEMM multiplies by
-          }
-          bias[n] = static_cast<float>(bsum);
-          colsum[n] = static_cast<float>(csum);
-        }
-        bias.resize(round_up(c.N, 8));
-        q.bias_off = push_f32(bias);
-        q.colsum_off = push_f32(colsum);
-        q.conv.bias = nullptr;
-        q.in = p.in;
-        q.in3 = stats;
-        q.name = p.name + "+" + q.name;
-      }
-      p.stats_only = 1;
-      p.out = stats;
-    }
-  }
-
-  // Statistics-only LayerNorm whose input is the stored output of a rows GEMM (ViT pre-norm
-  // blocks: the attention-out and MLP2 GEMMs, residual add in their epilogue) -> deleted.  That GEMM
-  // also writes per-(row, 64-column group) (mean, M2) partials from the values it holds in registers
-  // (ConvArgs::stats_out), and every block of a folded reader merges its rows' groups in a fixed
-  // order while its first operand tiles load (ConvArgs::row_parts): no launch, no re-read of the rows.
-  // The block-0 LayerNorm's input comes from the token assembly, which emits the same partials.
-  void stats_from_producer() {
-    const int nops = static_cast<int>(plan_.ops.size());
-    std::vector<std::vector<int>> readers(plan_.bufs.size());
-    for (int i = 0; i < nops; ++i)
-      for (int b : {plan_.ops[i].in, plan_.ops[i].in2, plan_.ops[i].in3})
-        if (b >= 0) readers[b].push_back(i);
-    std::vector<int> writer(plan_.bufs.size(), -1);  // latest op writing each buffer
-    std::vector<bool> drop(nops, false);
-    for (int i = 0; i < nops; ++i) {
-      PlanOp& p = plan_.ops[i];
-      const int w = p.kind == PlanOp::LAYERNORM && p.stats_only && p.in >= 0 ? writer[p.in] : -1;
-      if (w >= 0 && p.C == p.Cp && p.C % 64 == 0 && p.C <= 2048 && p.join < 0) {
-        PlanOp& q = plan_.ops[w];
-        const kern::ConvArgs& c = q.conv;
-        // rows GEMM (attention-out / MLP2), or the token assembly (block 0)
-        const bool gemm = q.kind == PlanOp::CONV && c.N == p.C && c.Ho * c.Wo == p.rows_per_sample && q.out2 < 0;
-        const bool tokens = q.kind == PlanOp::TOKENS && q.C == p.C && q.S + 1 == p.rows_per_sample;
-        bool ok = (gemm || tokens) && q.out == p.in && q.out_stats < 0 && q.join < 0;
-        for (int j : readers[p.out]) {
-          const PlanOp& r = plan_.ops[j];
-          ok = ok && j > i && r.kind == PlanOp::CONV && r.in3 == p.out && r.colsum_off != SIZE_MAX &&
-               r.conv.N % 8 == 0 && r.conv.K == p.C && r.join < 0;
-        }
-        if (ok && !readers[p.out].empty()) {
-          const int st = new_buf(static_cast<size_t>(p.rows_per_sample) * (p.C / 64) * 2 * 4);
-          q.out_stats = st;
-          q.name += "+stats";
-          for (int j : readers[p.out]) {
-            PlanOp& r = plan_.ops[j];
-            r.in3 = st;
-            r.in3_parts = 1;
-            r.eps = p.eps;
-          }
-          drop[i] = true;
-        }
-      }
-      for (int b : {p.out, p.out2, p.out3, p.out_f32})
-        if (b >= 0) writer[b] = i;
-    }
-    std::vector<PlanOp> out;
-    out.reserve(plan_.ops.size());
-    for (int i = 0; i < nops; ++i)
-      if (!drop[i]) out.push_back(std::move(plan_.ops[i]));
-    plan_.ops = std::move(out);
-  }
-
-  // Back-to-back 1x1 pair (ResNet-v2 bottleneck boundary).  A dual-store expand conv P writes the
-  // raw sum x (next residual) and a = act(bn(x)); when a's ONLY reader is a plain 1x1/s1 reduce conv
-  // Q, both become one CONV_PAIR op at P's position (Q has no other input, so computing it early is
-  // safe) and `a` is never stored: kernels/conv_pair.hip consumes it from LDS.  Rows of both weight
-  // matrices are permuted in place (kern::pair_permute_row) -- P and Q exist only inside the pair.
-  void permute_weight_rows(size_t off, int rows, int kpad, long long plane) {
-    const int planes = plane > 0 ? 2 : 1;
-    std::vector<uint16_t> tmp(static_cast<size_t>(rows) * kpad);
-    for (int pl = 0; pl < planes; ++pl) {
-      uint16_t* w = reinterpret_cast<uint16_t*>(plan_.params.data() + off) + static_cast<size_t>(pl) * plane;
-      std::memcpy(tmp.data(), w, tmp.size() * 2);
-      for (int n = 0; n < rows; ++n)
-        std::memcpy(w + static_cast<size_t>(kern::pair_permute_row(n)) * kpad, tmp.data() + static_cast<size_t>(n) * kpad,
-                    static_cast<size_t>(kpad) * 2);
-    }
-  }
-  static bool plain_1x1(const kern::ConvArgs& c) {
-    return c.KH == 1 && c.KW == 1 && c.stride == 1 && c.pad_h == 0 && c.pad_w == 0 && c.dil == 1 && c.H == c.Ho &&
-           c.W == c.Wo && c.K == c.Cin && c.Kpad == c.K;
-  }
-  // With other readers of `a` (a stage boundary: the next stage's projection shortcut reads it
-  // too) the pair also stores a (PlanOp::out3) and those readers keep reading it.
-  // Reduce widths up to 128: the kernel takes 256 (stage 2 -> 3) but at one block per CU it is
-  // faster than the two convs only at small batches (B=20: 43.3 vs 51.1 us; B=32: 76.4 vs 69.1).
-  static constexpr int kMaxPairN2 = 128;
-  void fuse_conv_pairs() {
-    const int nops = static_cast<int>(plan_.ops.size());
-    std::vector<std::vector<int>> readers(plan_.bufs.size());
-    for (int i = 0; i < nops; ++i)
-      for (int b : {plan_.ops[i].in, plan_.ops[i].in2, plan_.ops[i].in3})
-        if (b >= 0) readers[b].push_back(i);
-    std::vector<bool> drop(nops, false);
-    auto reduce_ok = [&](const PlanOp& p, const PlanOp& q) {
-      return q.kind == PlanOp::CONV && q.in == p.out2 && q.in2 < 0 && q.in3 < 0 && q.out >= 0 && q.out2 < 0 &&
-             q.out_f32 < 0 && q.conv.relu <= 1 && q.in_scale_off == SIZE_MAX && plain_1x1(q.conv) &&
-             q.conv.Cin == p.conv.N && q.conv.H == p.conv.Ho && q.conv.W == p.conv.Wo && q.join < 0 &&
-             q.conv.N <= kMaxPairN2 && kern::conv_pair_supported(p.conv.K, p.conv.N, q.conv.N);
-    };
-    for (int i = 0; i < nops; ++i) {
-      PlanOp& p = plan_.ops[i];
-      if (p.kind != PlanOp::CONV || p.in2 < 0 || p.out2 < 0 || p.s2_off == SIZE_MAX || p.out_f32 >= 0 ||
-          p.conv.relu != 0 || p.in_scale_off != SIZE_MAX || !plain_1x1(p.conv) || p.join >= 0)
-        continue;
-      const std::vector<int>& rd = readers[p.out2];
-      int j = -1;
-      for (int r : rd)
-        if (r > i && !drop[r] && reduce_ok(p, plan_.ops[r])) {
-          j = r;
-          break;
-        }
-      if (j < 0) continue;
-      bool others_ok = true;  // every other reader runs after the pair (at P's position) and reads a as an input
-      for (int r : rd)
-        if (r != j && (r <= i || plan_.ops[r].join >= 0)) others_ok = false;
-      if (!others_ok) continue;
-      const PlanOp& q = plan_.ops[j];
-      permute_weight_rows(p.w_off, static_cast<int>(round_up(p.conv.N, 128)), p.conv.Kpad, p.conv.wplane);
-      permute_weight_rows(q.w_off, static_cast<int>(round_up(q.conv.N, 128)), q.conv.Kpad, q.conv.wplane);
-      p.kind = PlanOp::CONV_PAIR;
-      p.name += "+" + q.name;
-      p.w2_off = q.w_off;
-      p.bias2_off = q.bias_off;
-      p.w2plane = q.conv.wplane;
-      p.n2 = q.conv.N;
-      p.pair_relu = q.conv.relu;
-      p.out3 = rd.size() > 1 ? p.out2 : -1;  // a stored for its other readers, else dropped
-      p.out2 = q.out;
-      p.flops_per_sample += q.flops_per_sample;
-      drop[j] = true;
-    }
-    std::vector<PlanOp> out;
-    out.reserve(plan_.ops.size());
-    for (int i = 0; i < nops; ++i)
-      if (!drop[i]) out.push_back(std::move(plan_.ops[i]));
-    plan_.ops = std::move(out);
-  }
-
-  // Pre-activation on load (opt-in, EngineOptions::bn_on_load).  A dual-store conv writes x (the raw sum: next residual) AND
-  // a = act(bn(x)) (the next unit's input).  When every reader of `a` is a 1x1 conv the LDS-DMA
-  // loop can run (K = Cin <= 2048, Cin % 64 == 0), those convs read x and apply bn+act to their
-  // operand fragments instead, and the producer stores x only: one activation-sized write and
-  // read fewer per unit (ResNet-v2 expand convs are store-bound).
-  void preact_on_load() {
-    const int nops = static_cast<int>(plan_.ops.size());
-    for (int i = 0; i < nops; ++i) {
-      PlanOp& p = plan_.ops[i];
-      if (p.kind != PlanOp::CONV || p.out < 0 || p.out2 < 0 || p.s2_off == SIZE_MAX) continue;
-      std::vector<int> readers;
-      bool ok = true;
-      for (int k = 0; k < nops && ok; ++k) {
-        if (k == i) continue;
-        const PlanOp& q = plan_.ops[k];
-        if (q.in2 == p.out2 || q.in3 == p.out2 || q.out == p.out2 || q.out2 == p.out2) ok = false;
-        if (q.in != p.out2) continue;
-        const kern::ConvArgs& c = q.conv;
-        ok = q.kind == PlanOp::CONV && c.KH == 1 && c.KW == 1 && c.pad_h == 0 && c.pad_w == 0 && c.K == c.Cin &&
-             c.Cin % 64 == 0 && c.K <= 2048 && q.in_scale_off == SIZE_MAX;
-        readers.push_back(k);
-      }
-      if (!ok || readers.empty()) continue;
-      for (int k : readers) {
-        PlanOp& q = plan_.ops[k];
-        q.in = p.out;
-        q.in_scale_off = p.s2_off;
-        q.in_shift_off = p.b2_off;
-        q.in_relu = p.conv.relu2;
-      }
-      p.out2 = -1;
-      p.s2_off = p.b2_off = SIZE_MAX;
-      p.conv.relu2 = 0;
-    }
-  }
-
-  // Branch concurrency: a conv whose output is first consumed two or more ops later (ResNet's
-  // projection shortcut: consumed as the residual of the unit's expand conv, after the reduce and
-  // 3x3 convs) is independent of the ops in between.  At serving batch sizes every one of those
-  // convs is latency-bound and leaves CUs idle, so the engine runs the branch on a second stream
-  // and joins it at its consumer.  One branch open at a time.
-  void mark_side_branches() {
-    const int nops = static_cast<int>(plan_.ops.size());
-    int open_until = -1;
-    for (int i = 0; i < nops; ++i) {
-      PlanOp& p = plan_.ops[i];
-      if (i <= open_until || p.kind != PlanOp::CONV || p.out < 0 || p.out_f32 >= 0 || p.out_stats >= 0) continue;
-      int j = -1;
-      for (int k = i + 1; k < nops && j < 0; ++k) {
-        const PlanOp& q = plan_.ops[k];
-        for (int b : {q.in, q.in2, q.in3})
-          if (b >= 0 && (b == p.out || b == p.out2)) j = k;
-      }
-      if (j < i + 2) continue;
-      p.join = j;
-      open_until = j;
-    }
-  }
-
-  void assign_arena() {
-    const int nops = static_cast<int>(plan_.ops.size());
-    for (int i = 0; i < nops; ++i) {
-      const PlanOp& p = plan_.ops[i];
-      for (int b : {p.out, p.out2, p.out3, p.out_stats})
-        if (b >= 0 && plan_.bufs[b].first_use < 0) plan_.bufs[b].first_use = i;
-      for (int b : {p.in, p.in2, p.in3, p.in4, p.in5, p.out, p.out2, p.out3, p.out_stats})
-        if (b >= 0) plan_.bufs[b].last_use = std::max(plan_.bufs[b].last_use, i);
-      // a side branch may still be reading its inputs until its join
-      if (p.join >= 0)
-        for (int b : {p.in, p.in2, p.in3, p.in4, p.in5})
-          if (b >= 0) plan_.bufs[b].last_use = std::max(plan_.bufs[b].last_use, p.join);
-    }
-    // Offsets: greedy by size (largest first, each at the lowest offset that does not overlap an
-    // already placed buffer whose lifetime intersects its own) -- for ResNet50 this packs the
-    // arena ~1.5x tighter than first-fit in program order, which keeps activations + weights inside
-    // the 256 MiB Infinity Cache.
-    std::vector<int> order;
-    for (size_t i = 0; i < plan_.bufs.size(); ++i)
-      if (plan_.bufs[i].first_use >= 0 || plan_.bufs[i].last_use >= 0) order.push_back(static_cast<int>(i));
-    auto bytes_of = [&](int bi) { return round_up(plan_.bufs[bi].bytes_per_sample * max_batch_, 256); };
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return bytes_of(a) > bytes_of(b); });
-    struct Placed {
-      size_t off, size;
-      int first, last;
-    };
-    std::vector<Placed> placed;
-    size_t top = 0;
-    for (int bi : order) {
-      PlanBuf& b = plan_.bufs[bi];
-      const size_t size = bytes_of(bi);
-      const int first = b.first_use < 0 ? 0 : b.first_use;
-      const int last = std::max(b.last_use, first);
-      std::vector<std::pair<size_t, size_t>> busy;  // ranges of lifetime-overlapping buffers
-      for (const Placed& q : placed)
-        if (q.first <= last && first <= q.last) busy.emplace_back(q.off, q.off + q.size);
-      std::sort(busy.begin(), busy.end());
-      size_t cand = 0;
-      for (const auto& r : busy) {
-        if (r.first >= cand + size) break;
-        cand = std::max(cand, r.second);
-      }
-      b.offset = cand;
-      placed.push_back(Placed{cand, size, first, last});
-      top = std::max(top, cand + size);
-    }
-    plan_.arena_bytes = top;
-    double fl = 0;
-    for (auto& p : plan_.ops) fl += p.flops_per_sample;
-    plan_.flops_per_sample = fl;
-  }
-
   const onnx::Model& m_;
   int max_batch_;
-  bool side_branches_ = false;
-  bool split_ = false;  // fp32 mode: split (hi, lo) activations and weights
-  bool bn_on_load_ = false;  // EngineOptions::bn_on_load (bf16 plans only)
-  bool fuse_pairs_ = true;   // EngineOptions::fuse_pairs
-  bool fuse_stem_pool_ = true;  // EngineOptions::fuse_stem_pool
-  bool fuse_gap_fc_ = false;    // EngineOptions::fuse_gap_fc
-  bool fold_layernorm_ = true;  // EngineOptions::fold_layernorm
-  bool ln_stats_epilogue_ = true;  // EngineOptions::ln_stats_epilogue
+  PlanOptions opt_;
   Plan plan_;
   std::vector<Val> vals_;
   std::unordered_map<std::string, int> vid_;
@@ -3660,15 +3174,10 @@ onnx::Model rewrite_conv_transpose(const onnx::Model& src) {
 
 }  // namespace
 
-Plan build_plan(const onnx::Model& m, int max_batch, bool side_branches, bool split, bool bn_on_load, bool fuse_pairs,
-                bool fuse_stem_pool, bool fuse_gap_fc, bool fold_layernorm, bool ln_stats_epilogue) {
-  if (has_conv_transpose(m)) {
-    const onnx::Model r = rewrite_conv_transpose(m);
-    return Planner(r, max_batch, side_branches, split, bn_on_load, fuse_pairs, fuse_stem_pool, fuse_gap_fc,
-                   fold_layernorm, ln_stats_epilogue).run();
-  }
-  return Planner(m, max_batch, side_branches, split, bn_on_load, fuse_pairs, fuse_stem_pool, fuse_gap_fc,
-                 fold_layernorm, ln_stats_epilogue).run();
+Plan build_plan(const onnx::Model& m, int max_batch, const PlanOptions& opt) {
+  const bool rw = has_conv_transpose(m);
+  const onnx::Model r = rw ? rewrite_conv_transpose(m) : onnx::Model();
+  return Planner(rw ? r : m, max_batch, opt).run();
 }
 
 std::string PlanReport::text() const {
@@ -3681,7 +3190,9 @@ std::string PlanReport::text() const {
 PlanReport plan_report(const onnx::Model& m, int max_batch, bool split) {
   const bool rw = has_conv_transpose(m);
   const onnx::Model r = rw ? rewrite_conv_transpose(m) : onnx::Model();
-  Planner p(rw ? r : m, max_batch, false, split, false);
+  PlanOptions opt;
+  opt.split = split;
+  Planner p(rw ? r : m, max_batch, opt);
   try {
     p.run();
   } catch (const std::exception& e) {

@@ -24,6 +24,9 @@
 //    broadcast, a finite fill above -1e4, a query row with no visible key, and a mask that is not an
 //    initializer -- folding of mask-building Slice / Cast subgraphs, cross-attention and KV caches
 //    are out of scope.
+//    Sibling Q/K/V MatMuls become one GEMM (N = 3*D); MatMul -> Add(bias) -> erf-GELU and
+//    MatMul -> Add(bias) -> Add(residual) fold into the GEMM epilogue; cls Expand/Concat + position
+//    Add -> one token-assembly kernel; LayerNormalization and Gather(token) -> row kernels.
 //  * token-id models: a rank-2 input [N, S] whose consumers all treat it as ids (Cast to an integer
 //    type, Gather indices, Equal / Greater / Less against a scalar) gets no ROWS_PREP;
 //    Gather(table, ids, axis 0) [+ Add(positions)] [+ Add(token-type row)] is one EMBED_TOKENS op
@@ -41,9 +44,6 @@
 //    export ReduceL2 -> Clip(min = eps) -> [Expand] -> Div) joins that op when the pooled vector has
 //    no other reader and is a POOL_TOKENS op with S = 1 anywhere else.  As the graph output the op
 //    writes fp32 straight into the output buffer.  Sum / max / last-token pooling: out of scope.
-//    Sibling Q/K/V MatMuls become one GEMM (N = 3*D); MatMul -> Add(bias) -> erf-GELU and
-//    MatMul -> Add(bias) -> Add(residual) fold into the GEMM epilogue; cls Expand/Concat + position
-//    Add -> one token-assembly kernel; LayerNormalization and Gather(token) -> row kernels.
 // Anything else falls back to standalone affine/add/relu kernels, or is rejected with a clear
 // error (the CPU executor still runs such models).
 #pragma once
@@ -62,6 +62,17 @@ struct PlanBuf {
   size_t bytes_per_sample = 0;  // scaled by the batch size at allocation time
   size_t offset = 0;            // arena offset (max batch), assigned by the planner
   int first_use = -1, last_use = -1;
+};
+
+// The pad test of a token-id model: a key is visible iff ((truncated ? trunc(id) : id) OP value) !=
+// negated, OP = op (0 Equal, 1 Greater, 2 Less) -- the pad_* arguments of kern::embed_tokens.
+struct PadTest {
+  int op = 0;
+  float value = 0.f;
+  bool negated = false, truncated = false;
+  bool operator==(const PadTest& o) const {
+    return op == o.op && value == o.value && negated == o.negated && truncated == o.truncated;
+  }
 };
 
 struct PlanOp {
@@ -88,12 +99,11 @@ struct PlanOp {
     EMBED_TOKENS,  // token ids (the fp32 graph input [S], in = -2) -> rows: out [S][C] = table[idx(id)] + pos + type
                   // with w_off = table [gidx = V][C] f32, shift_off = pos [S][C], bias_off = type [C] (C = stored
                   // width, Cp = the model's); key data for key-masked attention when out2 >= 0: out2 = kvis
-                  // f32 [S rounded up to 32], out3 = kend (one int), pad test visible = ((in_relu ? trunc(id)
-                  // : id) OP clip_lo) != is_max with OP = act (0 Equal, 1 Greater, 2 Less)
+                  // f32 [kern::key_pitch(S)], out3 = kend (one int), from the pad test `pad`
     POOL_TOKENS  // rows in [S][C] (Cp logical columns) -> one vector: out [C] (bf16 / split) or out_f32 [Cp] (the
-                 // graph output).  key_mask = 1: the mean over the visible tokens, sum / max(count, clip_lo),
+                 // graph output).  key_mask = 1: the mean over the visible tokens, sum / max(count, count_min),
                  // with in4 / in5 = the EMBED_TOKENS op's kvis / kend; else the mean of all S rows.
-                 // act = 1: then v / max(||v||_2, eps).  S = 1, act = 1: a row L2 normalisation
+                 // normalize: then v / max(||v||_2, eps).  S = 1, normalize: a row L2 normalisation
   } kind;
   std::string name;
   // buffers (-1 = none).  -2 = the graph input (f32 NCHW), -3 = the graph output (f32).
@@ -118,20 +128,20 @@ struct PlanOp {
   int S = 0, nh = 0, hd = 0, gidx = 0;
   int col[3] = {0, 0, 0}, ld[3] = {0, 0, 0};
   float fscale = 1.f, eps = 0.f;
-  // ATTENTION with a folded bias / mask: bias_off = fp32 table [bias_heads][S][S rounded up to 32] in
+  // ATTENTION with a folded bias / mask: bias_off = fp32 table [bias_heads][S][kern::key_pitch(S)] in
   // the kernel's exp2 units (kern::attention), bias_heads = 0 (none), 1 (shared) or nh; causal = 1:
   // key j visible to query i iff j <= i
   int bias_heads = 0, causal = 0;
   // ATTENTION with the request's key (padding) mask: in4 / in5 = the kvis / kend buffers of the plan's
   // EMBED_TOKENS op (kern::attention); combines with a bias table, never with causal
   int key_mask = 0, in4 = -1, in5 = -1;
+  PadTest pad;            // EMBED_TOKENS writing key data (out2 >= 0)
+  bool normalize = false;  // POOL_TOKENS
+  float count_min = 0.f;   // POOL_TOKENS with key_mask: lower bound of the count of visible tokens
   double flops_per_sample = 0;
   // Side branch: this op may run on a second stream, concurrently with the ops after it, until
   // op `join` (its first consumer) waits for it.  The arena keeps its inputs live until `join`.
   int join = -1;
-  // CONV: pre-activation on load (ConvArgs::in_scale/in_shift/in_relu), parameter offsets
-  size_t in_scale_off = SIZE_MAX, in_shift_off = SIZE_MAX;
-  int in_relu = 0;
   // CONV_PAIR: in = expand input [M][K1], in2 = residual, out = raw sum x (-1: not stored), out2 =
   // reduce output [M][n2]; conv/w_off/bias_off/s2_off/b2_off describe the expand conv and the BN of
   // the pre-activation, w2_off/bias2_off/w2plane/pair_relu the reduce conv.  Both weight matrices
@@ -175,18 +185,22 @@ struct PlanUnsupported : std::runtime_error {
   using std::runtime_error::runtime_error;
 };
 
+struct PlanOptions {
+  bool side_branches = false;  // mark independent convs to run on a second stream (PlanOp::join; extends
+                               // their inputs' lifetimes)
+  bool split = false;          // fp32 mode (Plan::split)
+  // the post-lowering passes, each named after its EngineOptions member
+  bool fuse_pairs = true;         // expand -> reduce 1x1 conv pairs become CONV_PAIR ops
+  bool fuse_stem_pool = true;     // stem conv + max pool in one STEM op
+  bool fuse_gap_fc = false;       // global pool + the FC head reading it in one GAP_FC op
+  bool fold_layernorm = true;     // LayerNorms read only by GEMMs become statistics ops (fp32 mode only)
+  bool ln_stats_epilogue = true;  // ... and those statistics come from the epilogue of the GEMM
+                                  // producing the LayerNorm's input where one does
+};
+
 // Build the plan for batches up to max_batch.  Throws PlanUnsupported on unsupported graphs, listing EVERY node
-// the engine cannot lower (not only the first).  side_branches: mark independent convs to run on
-// a second stream (PlanOp::join; extends their inputs' lifetimes).  split: fp32 mode (Plan::split).
-// fuse_pairs: lower expand -> reduce 1x1 conv pairs to CONV_PAIR ops (EngineOptions::fuse_pairs).
-// fuse_stem_pool: stem conv + max pool in one STEM op (EngineOptions::fuse_stem_pool).
-// fuse_gap_fc: global pool + the FC head reading it in one GAP_FC op (EngineOptions::fuse_gap_fc).
-// fold_layernorm: LayerNorms read only by GEMMs become statistics ops (EngineOptions::fold_layernorm).
-// ln_stats_epilogue: ... and those statistics come from the epilogue of the GEMM producing the
-// LayerNorm's input where one does (EngineOptions::ln_stats_epilogue).
-Plan build_plan(const onnx::Model& m, int max_batch, bool side_branches = false, bool split = false,
-                bool bn_on_load = false, bool fuse_pairs = true, bool fuse_stem_pool = true, bool fuse_gap_fc = false,
-                bool fold_layernorm = true, bool ln_stats_epilogue = true);
+// the engine cannot lower (not only the first).
+Plan build_plan(const onnx::Model& m, int max_batch, const PlanOptions& opt = {});
 
 // Load-time support report: which nodes the HIP planner cannot lower, and why.  `blocked` counts
 // nodes not tried because an input came from an unsupported node.

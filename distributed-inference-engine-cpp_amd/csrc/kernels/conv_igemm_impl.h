@@ -768,32 +768,12 @@ __device__ __forceinline__ void glds16(const uint16_t* g, uint16_t* l) {
                                    (__attribute__((address_space(3))) void*)l, 16, 0, 0);
 }
 
-// 8 bf16 (one MFMA operand fragment, 8 consecutive channels) -> act(v * s + h), re-rounded to bf16.
-__device__ __forceinline__ bf16x8 bn_act8(bf16x8 f, float4 s0, float4 s1, float4 h0, float4 h1, int relu) {
-  const uint4 q = __builtin_bit_cast(uint4, f);
-  float v[8];
-  unpack2(q.x, v[0], v[1]);
-  unpack2(q.y, v[2], v[3]);
-  unpack2(q.z, v[4], v[5]);
-  unpack2(q.w, v[6], v[7]);
-  const float sc[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-  const float sh[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-#pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    v[t] = fmaf(v[t], sc[t], sh[t]);
-    if (relu) v[t] = fmaxf(v[t], 0.f);
-  }
-  return __builtin_bit_cast(bf16x8, make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])));
-}
-
-constexpr int kBnlMaxK = 2048;  // pre-activation on load: channels staged in LDS
-
 // SPLIT (fp32 mode): each stage holds [A_hi][B_hi][A_lo][B_lo]; the lo tiles are DMA'd from the
 // planes wplane / xplane elements after the hi ones (zero-page rows stay zero-page), and every
 // fragment pair takes three MFMAs (hi*hi + lo*hi + hi*lo).
 // SK: the stream-K form (ConvArgs::sk > 0), a separate instantiation so that the plain kernels keep
 // their register allocation (the segment walk around the body cost ~50 VGPRs in the same kernel).
-template <int BM, int BN, int MODE, int STAGES, bool BNL = false, bool SPLIT = false, int BKS = BK, bool SK = false>
+template <int BM, int BN, int MODE, int STAGES, bool SPLIT = false, int BKS = BK, bool SK = false>
 __global__ __launch_bounds__(256) void conv_glds_kernel(const ConvArgs p, const int kt_per_split) {
   static_assert(BKS == 64 || BKS == 32, "K-step width");
   constexpr int CPR = BKS / 8;        // 16-byte chunks per LDS row
@@ -809,10 +789,9 @@ __global__ __launch_bounds__(256) void conv_glds_kernel(const ConvArgs p, const 
   // epilogue: the f32 tile, plus (fp32: ConvArgs::row_parts readers) the BM (mean, rstd) row cache
   constexpr int EPI_ELEMS = BM * BN * 2 + (SPLIT ? BM * 4 : 0);
   constexpr int LDS_ELEMS = STAGES * STAGE > EPI_ELEMS ? STAGES * STAGE : EPI_ELEMS;
-  // One LDS array: the stage ring / epilogue tile, then (BNL) the channel table.  No separate
-  // dummy arrays: a 1-stage split 64x64 block is exactly 32 KiB.
-  constexpr int BNL_ELEMS = BNL ? 2 * 2 * kBnlMaxK : 0;
-  __shared__ __attribute__((aligned(16))) uint16_t lds[LDS_ELEMS + BNL_ELEMS];
+  // One LDS array: the stage ring / epilogue tile.  No separate dummy arrays: a 1-stage split 64x64
+  // block is exactly 32 KiB.
+  __shared__ __attribute__((aligned(16))) uint16_t lds[LDS_ELEMS];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -825,15 +804,6 @@ __global__ __launch_bounds__(256) void conv_glds_kernel(const ConvArgs p, const 
                  int sk_first) {
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const int nk = kt_end - kt_begin;
-  // pre-activation on load: this slice's per-channel scale/shift in LDS (K = channels for 1x1)
-  float* bnl = reinterpret_cast<float*>(lds + LDS_ELEMS);  // BNL only: [scale | shift] x kBnlMaxK
-  if constexpr (BNL) {
-    for (int i = tid; i < nk * BKS; i += 256) {
-      bnl[i] = p.in_scale[kt_begin * BKS + i];
-      bnl[kBnlMaxK + i] = p.in_shift[kt_begin * BKS + i];
-    }
-    // visible to every wave after the main loop's first barrier
-  }
 
   // Per-lane DMA sources.  Wave `wave` fills rows [wave*R/4, (wave+1)*R/4) of each operand, 8 rows
   // per instruction (16 for 32-wide K-steps); lane L -> row L / CPR of that group, physical chunk L % CPR.
@@ -951,8 +921,8 @@ __global__ __launch_bounds__(256) void conv_glds_kernel(const ConvArgs p, const 
 #pragma unroll
     for (int j = 0; j < TM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // One K-step's MFMAs on the stage at A (K-step t of this slice, for the BNL channel table).
-  auto compute = [&](const uint16_t* A, int t) {
+  // One K-step's MFMAs on the stage at A.
+  auto compute = [&](const uint16_t* A) {
     const uint16_t* Bt = A + A_ELEMS;
 #pragma unroll
     for (int s = 0; s < KSUB; ++s) {
@@ -979,14 +949,6 @@ __global__ __launch_bounds__(256) void conv_glds_kernel(const ConvArgs p, const 
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afl[i], bfr[j], acc[i][j], 0, 0, 0);
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfl[j], acc[i][j], 0, 0, 0);
           }
-      }
-      if constexpr (BNL) {
-        const float* sc = bnl + t * BKS + chunk * 8;
-        const float4 s0 = *reinterpret_cast<const float4*>(sc), s1 = *reinterpret_cast<const float4*>(sc + 4);
-        const float4 h0 = *reinterpret_cast<const float4*>(sc + kBnlMaxK);
-        const float4 h1 = *reinterpret_cast<const float4*>(sc + kBnlMaxK + 4);
-#pragma unroll
-        for (int j = 0; j < TM; ++j) bfr[j] = bn_act8(bfr[j], s0, s1, h0, h1, p.in_relu);
       }
 #pragma unroll
       for (int i = 0; i < TN; ++i)
@@ -1020,7 +982,7 @@ __global__ __launch_bounds__(256) void conv_glds_kernel(const ConvArgs p, const 
       wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (mfma) compute(lds, t);
+      if (mfma) compute(lds);
     }
   } else {
     const bool dma = p.probe != 1, mfma = p.probe != 2;
@@ -1038,7 +1000,7 @@ __global__ __launch_bounds__(256) void conv_glds_kernel(const ConvArgs p, const 
       wr = wr + 1 == STAGES ? 0 : wr + 1;
       const uint16_t* A = lds + rd * STAGE;
       rd = rd + 1 == STAGES ? 0 : rd + 1;
-      if (mfma) compute(A, t);
+      if (mfma) compute(A);
     }
   }
   wait_vmcnt<0>();
@@ -1249,33 +1211,30 @@ bool launch_glds(int mode, dim3 grid, hipStream_t s, const ConvArgs& b, int kt_p
     if constexpr (STAGES <= 2) {
       if (b.split) {
         if constexpr (STAGES * (BM + BN) * BKS * 4 <= 160 * 1024)
-          hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 3, STAGES, false, true, BKS>), grid, dim3(256), 0, s, b, kt_per);
+          hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 3, STAGES, true, BKS>), grid, dim3(256), 0, s, b, kt_per);
         else
           return false;
-      } else if (!b.in_scale) {
-        hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 3, STAGES, false, false, BKS>), grid, dim3(256), 0, s, b, kt_per);
       } else {
-        return false;
+        hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 3, STAGES, false, BKS>), grid, dim3(256), 0, s, b, kt_per);
       }
       return true;
     } else {
       return false;
     }
   }
-  if (b.sk > 0) {  // stream-K: 1- and 2-stage loops, no pre-activation on load
+  if (b.sk > 0) {  // stream-K: 1- and 2-stage loops
     if constexpr (STAGES <= 2 && BKS == BK) {
-      if (b.in_scale) return false;
       if (b.split) {
         if constexpr (STAGES * (BM + BN) * BKS * 4 <= 160 * 1024) {
-          if (mode0) hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 0, STAGES, false, true, BKS, true>), grid, dim3(256), 0, s, b, kt_per);
-          else hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 2, STAGES, false, true, BKS, true>), grid, dim3(256), 0, s, b, kt_per);
+          if (mode0) hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 0, STAGES, true, BKS, true>), grid, dim3(256), 0, s, b, kt_per);
+          else hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 2, STAGES, true, BKS, true>), grid, dim3(256), 0, s, b, kt_per);
         } else {
           return false;
         }
       } else if (mode0) {
-        hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 0, STAGES, false, false, BKS, true>), grid, dim3(256), 0, s, b, kt_per);
+        hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 0, STAGES, false, BKS, true>), grid, dim3(256), 0, s, b, kt_per);
       } else {
-        hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 2, STAGES, false, false, BKS, true>), grid, dim3(256), 0, s, b, kt_per);
+        hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 2, STAGES, false, BKS, true>), grid, dim3(256), 0, s, b, kt_per);
       }
       return true;
     } else {
@@ -1284,16 +1243,13 @@ bool launch_glds(int mode, dim3 grid, hipStream_t s, const ConvArgs& b, int kt_p
   }
   if (b.split) {  // only ring depths whose doubled stages fit the LDS are instantiated
     if constexpr (STAGES * (BM + BN) * BKS * 4 <= 160 * 1024) {
-      if (mode0) hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 0, STAGES, false, true, BKS>), grid, dim3(256), 0, s, b, kt_per);
-      else hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 2, STAGES, false, true, BKS>), grid, dim3(256), 0, s, b, kt_per);
+      if (mode0) hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 0, STAGES, true, BKS>), grid, dim3(256), 0, s, b, kt_per);
+      else hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 2, STAGES, true, BKS>), grid, dim3(256), 0, s, b, kt_per);
     }
-  } else if (b.in_scale) {
-    if (mode0) hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 0, STAGES, true, false, BKS>), grid, dim3(256), 0, s, b, kt_per);
-    else hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 2, STAGES, true, false, BKS>), grid, dim3(256), 0, s, b, kt_per);
   } else if (mode0) {
-    hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 0, STAGES, false, false, BKS>), grid, dim3(256), 0, s, b, kt_per);
+    hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 0, STAGES, false, BKS>), grid, dim3(256), 0, s, b, kt_per);
   } else {
-    hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 2, STAGES, false, false, BKS>), grid, dim3(256), 0, s, b, kt_per);
+    hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 2, STAGES, false, BKS>), grid, dim3(256), 0, s, b, kt_per);
   }
   return true;
 }
@@ -1313,7 +1269,7 @@ hipError_t launch_cfg(const ConvArgs& a, hipStream_t s, int variant) {
   if (a.split) {  // plane distances of the split activations (weights: set by the planner)
     b.xplane = static_cast<long long>(a.B) * a.H * a.W * a.Cin;
     b.oplane = static_cast<long long>(a.M) * a.N;
-    if (a.wplane <= 0 || a.in_scale) return hipErrorInvalidValue;
+    if (a.wplane <= 0) return hipErrorInvalidValue;
   } else {
     b.xplane = b.oplane = 0;
   }
@@ -1323,7 +1279,7 @@ hipError_t launch_cfg(const ConvArgs& a, hipStream_t s, int variant) {
   if (a.sk > 0) {
     // stream-K: LDS-DMA loops only, in-kernel reduction only (a counter per tile), P blocks
     if (variant < 1 || variant > 5 || !a.counters || tiles > a.counters_n || !a.ws || a.N % 8 || a.tail > 0 ||
-        a.in_scale || a.row_parts || a.stats_out)
+        a.row_parts || a.stats_out)
       return hipErrorInvalidValue;
     b.counters = a.counters;
     b.splits = 1;
@@ -1344,15 +1300,10 @@ hipError_t launch_cfg(const ConvArgs& a, hipStream_t s, int variant) {
     }
     grid = dim3(g, 1);
   }
-  if (a.in_scale) {  // pre-activation on load: 1x1 convs in the LDS-DMA loop only
-    if (a.KH != 1 || a.KW != 1 || a.pad_h || a.pad_w || a.K != a.Cin || a.K > kBnlMaxK || a.Cin % BK || !a.in_shift)
-      return hipErrorInvalidValue;
-    if (variant == 0) variant = 1;  // the register-staged loop has no pre-activation: 2-stage ring
-  }
   if (variant == 6) {  // spatially tiled 3x3/s1/p1 (64x64 tile only): split-K over channel slices
     if constexpr (BM == 64 && BN == 64) {
       if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.dil != 1 || a.pad_h != 1 || a.pad_w != 1 || a.H != a.Ho ||
-          a.W != a.Wo || a.Cin % BK || a.K != 9 * a.Cin || a.Kpad != a.K || a.N % 8 || !a.zeros || a.in_scale)
+          a.W != a.Wo || a.Cin % BK || a.K != 9 * a.Cin || a.Kpad != a.K || a.N % 8 || !a.zeros)
         return hipErrorInvalidValue;
       const int nsl = a.Cin / BK;
       const int sp = std::max(1, std::min(a.splits, nsl));
@@ -1388,7 +1339,6 @@ hipError_t launch_cfg(const ConvArgs& a, hipStream_t s, int variant) {
     // BKS = 32>, at the 1-stage footprint, and a 1-stage loop that also touched the next K-step's
     // lines toward L2 with 4-byte LDS-DMA loads: both slower, profiles/r2_feed_calibration.md.)
     constexpr int kStageBytes = (BM + BN) * BK * 2;
-    if (a.in_scale && variant == 4) return hipErrorInvalidValue;  // 6 stages + the channel table exceed the LDS
     // split stages are twice as large: 128x128 fits 2 stages, 64-wide tiles 3-4 (160 KiB LDS)
     const int np = a.split ? 2 : 1;
     const int stages = variant == 1 ? 2 : variant == 2 ? 3 : variant == 3 ? 4 : variant == 4 ? 6 : 1;
@@ -1553,7 +1503,7 @@ inline hipError_t launch_wide(const ConvArgs& a, hipStream_t s) {
   constexpr int BM = 256, BN = 128;
   const bool dense = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad_h == 0 && a.pad_w == 0 && a.H == a.Ho &&
                      a.W == a.Wo && a.K % BK == 0 && a.Cin == a.K && a.Kpad == a.K;
-  if (!dense || !a.split || a.in_scale || !a.zeros || a.wplane <= 0 || a.N % 8) return hipErrorInvalidValue;
+  if (!dense || !a.split || !a.zeros || a.wplane <= 0 || a.N % 8) return hipErrorInvalidValue;
   const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
   const int nk = a.Kpad / BK;
   const int splits = std::max(1, std::min(a.splits, nk));

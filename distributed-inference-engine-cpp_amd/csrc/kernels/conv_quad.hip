@@ -199,7 +199,7 @@ __global__ __launch_bounds__(kQuadThreads) void conv3x3_quad_kernel(const ConvAr
 hipError_t launch_tile_quad(const ConvArgs& a, hipStream_t s, int tile) {
   if (tile != TILE_64x64) return hipErrorInvalidValue;
   if (a.KH != 3 || a.KW != 3 || a.stride != 1 || a.dil != 1 || a.pad_h != 1 || a.pad_w != 1 || a.H != a.Ho ||
-      a.W != a.Wo || a.Cin % BK || a.K != 9 * a.Cin || a.Kpad != a.K || a.N % 8 || !a.zeros || a.in_scale ||
+      a.W != a.Wo || a.Cin % BK || a.K != 9 * a.Cin || a.Kpad != a.K || a.N % 8 || !a.zeros ||
       a.row_stats || a.row_parts || a.stats_out || a.sk || a.tail)
     return hipErrorInvalidValue;
   if (a.split && a.wplane <= 0) return hipErrorInvalidValue;

@@ -87,9 +87,9 @@ hipError_t launch_tile_skinny(const ConvArgs& a, hipStream_t s, int tile) {
   const bool dense = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad_h == 0 && a.pad_w == 0 && a.H == a.Ho &&
                      a.W == a.Wo && a.Cin == a.K && a.K <= a.Kpad;
   // rows <= 32, whole 32-wide K-steps per wave, 8-channel epilogue groups, no split-K, no LayerNorm
-  // statistics / pre-activation on load (those belong to the row GEMMs of the tiled kernels)
+  // statistics (those belong to the row GEMMs of the tiled kernels)
   if (!dense || a.M < 1 || a.M > kSkRows || a.K % (32 * kSkWaves) != 0 || a.N % 8 != 0 || a.splits > 1 ||
-      a.in_scale || a.row_parts || a.stats_out || a.tail || (a.split && a.wplane <= 0))
+      a.row_parts || a.stats_out || a.tail || (a.split && a.wplane <= 0))
     return hipErrorInvalidValue;
   ConvArgs b = a;
   b.splits = 1;

@@ -46,12 +46,6 @@ struct ConvArgs {
   // that round up to it; only the first *live samples are real, so output tiles that hold padding
   // samples only are skipped (their rows stay undefined; every op is per-sample).
   const long long* live = nullptr;
-  // Pre-activation on load (1x1 convs, K = Cin <= 2048, LDS-DMA loop): the input operand is
-  // act(x * in_scale[c] + in_shift[c]) of the stored x (ResNet-v2's BN+ReLU of the unit input is
-  // applied here instead of being stored a second time by the producing conv).
-  const float* in_scale = nullptr;
-  const float* in_shift = nullptr;
-  int in_relu = 0;
   // relu == 3: Clip(clip_lo, clip_hi) (ReLU6 = Clip(0, 6)) instead of ReLU / GELU
   float clip_lo = 0.f, clip_hi = 0.f;
   // LayerNorm folded into the GEMM (rows GEMMs): x is the LayerNorm INPUT, the weights carry gamma,
@@ -391,6 +385,8 @@ hipError_t attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, ui
                      int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t s, int split = 0,
                      const float* bias = nullptr, int bias_heads = 0, int Sp = 0, int causal = 0,
                      const float* kvis = nullptr, const int* kend = nullptr);
+// Row pitch Sp of the bias table and of the key data kvis for sequences of S keys: S rounded up to 32.
+inline int key_pitch(int S) { return (S + 31) / 32 * 32; }
 // Embedding lookup on fp32 token ids [B][S]: out[b, s, :] = table[idx(ids[b, s])] + pos[s] + type,
 // summed in fp32, stored as bf16 rows [B*S][C] (split: hi / lo planes).  idx = k::token_index
 // (common.h): truncate, clamp to [0, V - 1], NaN -> 0 -- never out of bounds, whatever the input

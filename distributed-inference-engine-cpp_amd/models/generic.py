@@ -504,7 +504,7 @@ def build_ops_zoo(seed: int = 0, opset: int = 13) -> Tuple[bytes, Dict[str, np.n
         return g.node("Conv", [inp, w, b], name=name, kernel_shape=[k, k], pads=[pad] * 4)
 
     # relu first so the graph input is materialised once; Pad(1) folded into the 3x3 conv (pads 0)
-    h = g.node("Relu", [x], name="in_relu")
+    h = g.node("Relu", [x], name="relu_in")
     h = g.node("Pad", [h, g.const(np.array([0, 0, 1, 1, 0, 0, 1, 1], np.int64), "pad1")], name="pad1", mode="constant")
     h = g.node("HardSwish", [conv(h, "conv1", s["in_ch"], 16, 3, 0)], name="hswish")
     # asymmetric Pad before a MaxPool: not foldable (zeros vs -inf) -> a pad pass; 17x17 -> 8x8
