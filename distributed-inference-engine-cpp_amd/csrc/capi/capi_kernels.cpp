@@ -147,6 +147,89 @@ int die_kern_gap(uint64_t x, uint64_t out, uint64_t out_f32, uint64_t scale, uin
                                                nullptr, split));
 }
 
+// die_kern_pool2d plus the live batch, the fused per-channel affine on the pooled value and act (0 = none)
+int die_kern_pool2d_ex(uint64_t x, uint64_t y, int B, int H, int W, int C, int Ho, int Wo, int kh, int kw, int sh,
+                       int sw, int ph, int pw, int is_max, int cip, uint64_t stream, int split, uint64_t live,
+                       uint64_t scale, uint64_t shift, int act) {
+  return static_cast<int>(kern::pool2d(P<const uint16_t>(x), P<uint16_t>(y), B, H, W, C, Ho, Wo, kh, kw, sh, sw, ph,
+                                       pw, is_max, cip, S(stream), P<const long long>(live), P<const float>(scale),
+                                       P<const float>(shift), act, split));
+}
+
+// die_kern_gap plus the live batch and the reduction mode (0 mean, 1 sum, 2 max)
+int die_kern_gap_ex(uint64_t x, uint64_t out, uint64_t out_f32, uint64_t scale, uint64_t shift, int relu, int B, int HW,
+                    int C, uint64_t stream, int split, uint64_t live, int mode) {
+  return static_cast<int>(kern::global_avgpool(P<const uint16_t>(x), P<uint16_t>(out), P<float>(out_f32),
+                                               P<const float>(scale), P<const float>(shift), relu, B, HW, C, S(stream),
+                                               P<const long long>(live), split, mode));
+}
+
+// ---- generic kernels (kernels/generic.hip) and batched MatMul (kernels/bmm.hip); live 0 = none ----
+int die_kern_rows_prep(uint64_t x, uint64_t y, long long R, int F, int Fp, uint64_t stream, int split) {
+  return static_cast<int>(kern::rows_prep(P<const float>(x), P<uint16_t>(y), R, F, Fp, S(stream), split));
+}
+
+int die_kern_input_prep_wide(uint64_t x, uint64_t scale, uint64_t shift, uint64_t out, int B, int C, int H, int W,
+                             int Cp, uint64_t stream, int split) {
+  return static_cast<int>(kern::input_prep_wide(P<const float>(x), P<const float>(scale), P<const float>(shift),
+                                                P<uint16_t>(out), B, C, H, W, Cp, S(stream), split));
+}
+
+int die_kern_copy_cols(uint64_t x, long long xplane, int ldx, int colx, uint64_t y, long long yplane, int ldy, int coly,
+                       long long R, int ncols, uint64_t stream, int split) {
+  return static_cast<int>(kern::copy_cols(P<const uint16_t>(x), xplane, ldx, colx, P<uint16_t>(y), yplane, ldy, coly, R,
+                                          ncols, S(stream), split));
+}
+
+int die_kern_binary_rows(uint64_t x, uint64_t y, uint64_t out, long long R, int C, long long rows_per_sample, int ymode,
+                         int op, int act, float a, float b, uint64_t stream, uint64_t live, int split, int Cl) {
+  return static_cast<int>(kern::binary_rows(P<const uint16_t>(x), P<const uint16_t>(y), P<uint16_t>(out), R, C,
+                                            rows_per_sample, ymode, op, act, a, b, S(stream), P<const long long>(live),
+                                            split, Cl));
+}
+
+int die_kern_unary_rows(uint64_t x, uint64_t scale, uint64_t shift, uint64_t y, long long R, int C, int act, float a,
+                        float b, uint64_t stream, uint64_t live, long long rows_per_sample, int split, int Cl) {
+  return static_cast<int>(kern::unary_rows(P<const uint16_t>(x), P<const float>(scale), P<const float>(shift),
+                                           P<uint16_t>(y), R, C, act, a, b, S(stream), P<const long long>(live),
+                                           rows_per_sample, split, Cl));
+}
+
+int die_kern_where_rows(uint64_t c, uint64_t a, uint64_t b, float av, float bv, uint64_t out, long long R, int C,
+                        uint64_t stream, uint64_t live, long long rows_per_sample, int split, int Cl) {
+  return static_cast<int>(kern::where_rows(P<const uint16_t>(c), P<const uint16_t>(a), P<const uint16_t>(b), av, bv,
+                                           P<uint16_t>(out), R, C, S(stream), P<const long long>(live), rows_per_sample,
+                                           split, Cl));
+}
+
+int die_kern_resize_nhwc(uint64_t x, uint64_t y, int B, int H, int W, int C, int Ho, int Wo, float scale_h,
+                         float scale_w, int coord, int mode, int nearest, uint64_t stream, uint64_t live, int split) {
+  return static_cast<int>(kern::resize_nhwc(P<const uint16_t>(x), P<uint16_t>(y), B, H, W, C, Ho, Wo, scale_h, scale_w,
+                                            coord, mode, nearest, S(stream), P<const long long>(live), split));
+}
+
+int die_kern_pad_nhwc(uint64_t x, uint64_t y, int B, int H, int W, int C, int Ho, int Wo, int t, int l, uint64_t stream,
+                      int split, int sy, int sx) {
+  return static_cast<int>(kern::pad_nhwc(P<const uint16_t>(x), P<uint16_t>(y), B, H, W, C, Ho, Wo, t, l, S(stream),
+                                         split, sy, sx));
+}
+
+int die_kern_rows_to_f32(uint64_t x, uint64_t y, long long R, int C, int ld, uint64_t stream, int split) {
+  return static_cast<int>(kern::rows_to_f32(P<const uint16_t>(x), P<float>(y), R, C, ld, S(stream), split));
+}
+
+int die_kern_nhwc_to_nchw_strided(uint64_t x, uint64_t y, int B, int H, int W, int C, int Cs, uint64_t stream,
+                                  int split) {
+  return static_cast<int>(kern::nhwc_to_nchw_f32_strided(P<const uint16_t>(x), P<float>(y), B, H, W, C, Cs, S(stream),
+                                                         split));
+}
+
+int die_kern_bmm_rows(uint64_t A, uint64_t Bm, uint64_t C, int batch, int M, int N, int K, int lda, int ldb, int ldc,
+                      uint64_t stream, uint64_t live, int split) {
+  return static_cast<int>(kern::bmm_rows(P<const uint16_t>(A), P<const uint16_t>(Bm), P<uint16_t>(C), batch, M, N, K,
+                                         lda, ldb, ldc, S(stream), P<const long long>(live), split));
+}
+
 int die_kern_affine(uint64_t x, uint64_t z, uint64_t scale, uint64_t shift, int act, uint64_t y, long long M, int C,
                     uint64_t stream, int split) {
   return static_cast<int>(kern::affine_act(P<const uint16_t>(x), P<const uint16_t>(z), P<const float>(scale),

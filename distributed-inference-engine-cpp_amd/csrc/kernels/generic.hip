@@ -83,9 +83,10 @@ __global__ void copy_cols_kernel(const uint16_t* __restrict__ x, long long xplan
   }
 }
 
-// Activation codes (kernels.h unary_rows).  The transcendental ones use the accurate libm forms
-// (not the __expf-style intrinsics): they also serve the fp32 (split) mode, whose values carry
-// ~16 significant bits.
+// Activation codes (kernels.h unary_rows).  The transcendental ones use the accurate libm forms:
+// they also serve the fp32 (split) mode, whose values carry ~16 significant bits.  The exceptions
+// are GELU (gelu_erf, common.h) and the sigmoid's __expf, both within the per-element
+// bars that tests/test_gpu_generic_kernels.py holds every code to against float64.
 __device__ __forceinline__ float apply_act(float v, int act, float a, float b) {
   switch (act) {
     case 1: return fmaxf(v, 0.f);

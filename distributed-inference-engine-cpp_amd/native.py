@@ -704,6 +704,33 @@ def _sig_kernels():
     L.die_kern_pool2d.argtypes = [u64, u64] + [i] * 14 + [u64, i]
     L.die_kern_gap.restype = i
     L.die_kern_gap.argtypes = [u64] * 5 + [i] * 4 + [u64, i]
+    L.die_kern_pool2d_ex.restype = i
+    L.die_kern_pool2d_ex.argtypes = [u64, u64] + [i] * 14 + [u64, i, u64, u64, u64, i]
+    L.die_kern_gap_ex.restype = i
+    L.die_kern_gap_ex.argtypes = [u64] * 5 + [i] * 4 + [u64, i, u64, i]
+    ll, f = C.c_longlong, C.c_float
+    L.die_kern_rows_prep.restype = i
+    L.die_kern_rows_prep.argtypes = [u64, u64, ll, i, i, u64, i]
+    L.die_kern_input_prep_wide.restype = i
+    L.die_kern_input_prep_wide.argtypes = [u64] * 4 + [i] * 5 + [u64, i]
+    L.die_kern_copy_cols.restype = i
+    L.die_kern_copy_cols.argtypes = [u64, ll, i, i, u64, ll, i, i, ll, i, u64, i]
+    L.die_kern_binary_rows.restype = i
+    L.die_kern_binary_rows.argtypes = [u64, u64, u64, ll, i, ll, i, i, i, f, f, u64, u64, i, i]
+    L.die_kern_unary_rows.restype = i
+    L.die_kern_unary_rows.argtypes = [u64] * 4 + [ll, i, i, f, f, u64, u64, ll, i, i]
+    L.die_kern_where_rows.restype = i
+    L.die_kern_where_rows.argtypes = [u64, u64, u64, f, f, u64, ll, i, u64, u64, ll, i, i]
+    L.die_kern_resize_nhwc.restype = i
+    L.die_kern_resize_nhwc.argtypes = [u64, u64] + [i] * 6 + [f, f, i, i, i, u64, u64, i]
+    L.die_kern_pad_nhwc.restype = i
+    L.die_kern_pad_nhwc.argtypes = [u64, u64] + [i] * 8 + [u64, i, i, i]
+    L.die_kern_rows_to_f32.restype = i
+    L.die_kern_rows_to_f32.argtypes = [u64, u64, ll, i, i, u64, i]
+    L.die_kern_nhwc_to_nchw_strided.restype = i
+    L.die_kern_nhwc_to_nchw_strided.argtypes = [u64, u64] + [i] * 5 + [u64, i]
+    L.die_kern_bmm_rows.restype = i
+    L.die_kern_bmm_rows.argtypes = [u64] * 3 + [i] * 7 + [u64, u64, i]
     L.die_kern_affine.restype = i
     L.die_kern_affine.argtypes = [u64] * 4 + [i, u64, C.c_longlong, i, u64, i]
     L.die_kern_nhwc_to_nchw.restype = i

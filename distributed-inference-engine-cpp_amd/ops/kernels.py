@@ -255,31 +255,63 @@ def input_prep(x_nchw, scale=None, shift=None, cp=4, split=False):
     return _out(out, split)
 
 
-def pool2d_nhwc(x, k, stride, pad, is_max=True, count_include_pad=False, split=False):
+def _live(live, dev):
+    """The device-side live batch (kernels.h `live`): an int64 scalar on the device, None = all samples."""
     import torch
 
+    return None if live is None else torch.tensor([int(live)], dtype=torch.int64, device=dev)
+
+
+def _f32(v):
+    return None if v is None else v.float().contiguous()
+
+
+def _storage(out, shape, split, dev):
+    """Raw output storage: bf16 `shape`, or the hi / lo planes [2, *shape] in fp32 mode.  A caller's
+    pre-filled `out` is written in place (what a kernel leaves alone stays as it was)."""
+    import torch
+
+    full = ((2,) if split else ()) + tuple(shape)
+    if out is None:
+        return torch.empty(full, dtype=torch.bfloat16, device=dev)
+    if tuple(out.shape) != full or out.dtype != torch.bfloat16 or not out.is_contiguous():
+        raise ValueError("out must be contiguous bf16 %s, got %s %s" % (full, out.dtype, tuple(out.shape)))
+    return out
+
+
+def _pair(v):
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
+def pool2d_nhwc(x, k, stride, pad, is_max=True, count_include_pad=False, split=False, scale=None, shift=None,
+                act=0, live=None, out=None):
+    """k / stride / pad: one int or (h, w).  scale / shift [C] fp32: the fused per-channel affine on the
+    pooled value, then act (1 = ReLU).  live / out: as the generic kernels below take them."""
     B, H, W, C = x.shape
-    Ho = (H + 2 * pad - k) // stride + 1
-    Wo = (W + 2 * pad - k) // stride + 1
-    y = torch.empty(((2,) if split else ()) + (B, Ho, Wo, C), dtype=torch.bfloat16, device=x.device)
-    xin = _in(x, split)
-    rc = native.kernels().die_kern_pool2d(_ptr(xin), _ptr(y), B, H, W, C, Ho, Wo, k, k, stride, stride, pad,
-                                          pad, int(is_max), int(count_include_pad), _stream(), int(split))
+    (kh, kw), (sh, sw), (ph, pw) = _pair(k), _pair(stride), _pair(pad)
+    Ho = (H + 2 * ph - kh) // sh + 1
+    Wo = (W + 2 * pw - kw) // sw + 1
+    y = _storage(out, (B, Ho, Wo, C), split, x.device)
+    xin, sc, sf, lv = _in(x, split), _f32(scale), _f32(shift), _live(live, x.device)
+    rc = native.kernels().die_kern_pool2d_ex(_ptr(xin), _ptr(y), B, H, W, C, Ho, Wo, kh, kw, sh, sw, ph, pw,
+                                             int(is_max), int(count_include_pad), _stream(), int(split), _ptr(lv),
+                                             _ptr(sc), _ptr(sf), int(act))
     _check(rc, "pool2d")
     return _out(y, split)
 
 
-def global_avgpool_nhwc(x, scale=None, shift=None, relu=False, split=False):
+def global_avgpool_nhwc(x, scale=None, shift=None, relu=False, split=False, mode=0, live=None, out=None):
+    """mode: 0 mean, 1 sum, 2 max over the H*W pixels (after the optional per-pixel relu(x*scale+shift))."""
     import torch
 
     B, H, W, C = x.shape
-    out = torch.empty(((2,) if split else ()) + (B, C), dtype=torch.bfloat16, device=x.device)
+    o = _storage(out, (B, C), split, x.device)
     out32 = torch.empty((B, C), dtype=torch.float32, device=x.device)
-    xin = _in(x, split)
-    rc = native.kernels().die_kern_gap(_ptr(xin), _ptr(out), _ptr(out32), _ptr(scale), _ptr(shift),
-                                       int(relu), B, H * W, C, _stream(), int(split))
+    xin, lv = _in(x, split), _live(live, x.device)
+    rc = native.kernels().die_kern_gap_ex(_ptr(xin), _ptr(o), _ptr(out32), _ptr(scale), _ptr(shift),
+                                          int(relu), B, H * W, C, _stream(), int(split), _ptr(lv), int(mode))
     _check(rc, "global_avgpool")
-    return _out(out, split), out32
+    return _out(o, split), out32
 
 
 def affine_act(x, scale=None, shift=None, z=None, relu=False, split=False):
@@ -677,3 +709,148 @@ def softmax_rows(x, split=False):
     rc = native.kernels().die_kern_softmax(_ptr(xin), _ptr(y), _ptr(yf), rows, C, _stream(), int(split))
     _check(rc, "softmax_rows")
     return (join_planes(y) if split else y.float()), yf
+
+
+# ---- generic row / image kernels and batched MatMul (csrc/kernels/generic.hip, bmm.hip) -------------
+# Inputs are values (bf16 tensors, or any float dtype with split: converted to hi / lo planes).
+# `out`: optional pre-filled raw storage (_storage) the kernel writes in place, so a caller can see
+# what it left untouched; `live`: optional int, only the first `live` samples are computed.  Each
+# returns the stored values (bf16, or the fp32 hi + lo with split).
+
+def rows_prep(x, Fp, split=False, out=None):
+    """fp32 [R, F] -> stored rows [R, Fp] (Fp % 8 == 0, pad columns 0)."""
+    R, F = x.shape
+    y = _storage(out, (R, Fp), split, x.device)
+    xin = _f32(x)
+    rc = native.kernels().die_kern_rows_prep(_ptr(xin), _ptr(y), R, F, int(Fp), _stream(), int(split))
+    _check(rc, "rows_prep")
+    return _out(y, split)
+
+
+def input_prep_wide(x_nchw, Cp, scale=None, shift=None, split=False, out=None):
+    """fp32 NCHW [B, C, H, W] -> x * scale[c] + shift[c] -> NHWC [B, H, W, Cp] (Cp % 8 == 0, pad channels 0)."""
+    B, C, H, W = x_nchw.shape
+    y = _storage(out, (B, H, W, Cp), split, x_nchw.device)
+    xin, sc, sf = _f32(x_nchw), _f32(scale), _f32(shift)
+    rc = native.kernels().die_kern_input_prep_wide(_ptr(xin), _ptr(sc), _ptr(sf), _ptr(y), B, C, H, W, int(Cp),
+                                                   _stream(), int(split))
+    _check(rc, "input_prep_wide")
+    return _out(y, split)
+
+
+def copy_cols(x, y, colx, coly, ncols, split=False):
+    """y[r, coly + j] = x[r, colx + j], j < ncols.  x and y are raw storage: bf16 [R, ld], or the planes
+    [2, R, ld] with split; either may be a row slice of a taller tensor (the plane distance is
+    stride(0), the pitch stride(-2)).  y is written in place and returned."""
+    R = x.shape[-2]
+    for t in (x, y):
+        if t.stride(-1) != 1 or t.shape[-2] != R or t.dim() != (3 if split else 2):
+            raise ValueError("copy_cols takes raw rows [R, ld] (split: [2, R, ld]) with unit column stride")
+    xp, yp = (int(x.stride(0)), int(y.stride(0))) if split else (0, 0)
+    rc = native.kernels().die_kern_copy_cols(_ptr(x), xp, int(x.stride(-2)), int(colx), _ptr(y), yp, int(y.stride(-2)),
+                                             int(coly), R, int(ncols), _stream(), int(split))
+    _check(rc, "copy_cols")
+    return y
+
+
+def binary_rows(x, y, op, ymode=0, rows_per_sample=1, act=0, a=0.0, b=0.0, Cl=0, live=None, split=False, out=None):
+    """act(x op y) over rows [R, C]; ymode 1: y [R / rows_per_sample, C], one row per sample.
+    op / act codes and Cl: kernels.h binary_rows / unary_rows."""
+    R, C = x.shape
+    o = _storage(out, (R, C), split, x.device)
+    xin, yin, lv = _in(x, split), _in(y, split), _live(live, x.device)
+    rc = native.kernels().die_kern_binary_rows(_ptr(xin), _ptr(yin), _ptr(o), R, C, int(rows_per_sample), int(ymode),
+                                               int(op), int(act), float(a), float(b), _stream(), _ptr(lv), int(split),
+                                               int(Cl))
+    _check(rc, "binary_rows")
+    return _out(o, split)
+
+
+def unary_rows(x, act, a=0.0, b=0.0, scale=None, shift=None, Cl=0, live=None, rows_per_sample=0, split=False,
+               out=None):
+    """act(x * scale[c] + shift[c]) over rows [R, C] (kernels.h unary_rows for the codes and Cl)."""
+    R, C = x.shape
+    y = _storage(out, (R, C), split, x.device)
+    xin, sc, sf, lv = _in(x, split), _f32(scale), _f32(shift), _live(live, x.device)
+    rc = native.kernels().die_kern_unary_rows(_ptr(xin), _ptr(sc), _ptr(sf), _ptr(y), R, C, int(act), float(a),
+                                              float(b), _stream(), _ptr(lv), int(rows_per_sample), int(split), int(Cl))
+    _check(rc, "unary_rows")
+    return _out(y, split)
+
+
+def where_rows(cond, a, b, Cl=0, live=None, rows_per_sample=1, split=False, out=None):
+    """cond != 0 ? a : b over rows [R, C]; a / b: a tensor like cond, or a Python scalar."""
+    import torch
+
+    R, C = cond.shape
+    o = _storage(out, (R, C), split, cond.device)
+    cin, lv = _in(cond, split), _live(live, cond.device)
+    ain = _in(a, split) if torch.is_tensor(a) else None
+    bin_ = _in(b, split) if torch.is_tensor(b) else None
+    rc = native.kernels().die_kern_where_rows(_ptr(cin), _ptr(ain), _ptr(bin_), 0.0 if ain is not None else float(a),
+                                              0.0 if bin_ is not None else float(b), _ptr(o), R, C, _stream(),
+                                              _ptr(lv), int(rows_per_sample), int(split), int(Cl))
+    _check(rc, "where_rows")
+    return _out(o, split)
+
+
+def resize_nhwc(x, Ho, Wo, scale_h, scale_w, coord=0, mode=0, nearest=0, live=None, split=False, out=None):
+    """ONNX Resize of NHWC [B, H, W, C] to [B, Ho, Wo, C] (kernels.h resize_nhwc for the codes)."""
+    B, H, W, C = x.shape
+    y = _storage(out, (B, Ho, Wo, C), split, x.device)
+    xin, lv = _in(x, split), _live(live, x.device)
+    rc = native.kernels().die_kern_resize_nhwc(_ptr(xin), _ptr(y), B, H, W, C, int(Ho), int(Wo), float(scale_h),
+                                               float(scale_w), int(coord), int(mode), int(nearest), _stream(),
+                                               _ptr(lv), int(split))
+    _check(rc, "resize_nhwc")
+    return _out(y, split)
+
+
+def pad_nhwc(x, Ho, Wo, t, l, sy=1, sx=1, split=False, out=None):
+    """NHWC [B, H, W, C] placed at (t, l) of zeros [B, Ho, Wo, C], input pixels sy / sx apart."""
+    B, H, W, C = x.shape
+    y = _storage(out, (B, Ho, Wo, C), split, x.device)
+    xin = _in(x, split)
+    rc = native.kernels().die_kern_pad_nhwc(_ptr(xin), _ptr(y), B, H, W, C, int(Ho), int(Wo), int(t), int(l),
+                                            _stream(), int(split), int(sy), int(sx))
+    _check(rc, "pad_nhwc")
+    return _out(y, split)
+
+
+def rows_to_f32(x, C, split=False):
+    """Stored rows [R, ld] -> fp32 [R, C] (their first C columns)."""
+    import torch
+
+    R, ld = x.shape
+    y = torch.empty((R, C), dtype=torch.float32, device=x.device)
+    xin = _in(x, split)
+    rc = native.kernels().die_kern_rows_to_f32(_ptr(xin), _ptr(y), R, int(C), ld, _stream(), int(split))
+    _check(rc, "rows_to_f32")
+    return y
+
+
+def nhwc_to_nchw_f32_strided(x, C, split=False):
+    """Stored NHWC [B, H, W, Cs] -> fp32 NCHW [B, C, H, W] (the first C channels)."""
+    import torch
+
+    B, H, W, Cs = x.shape
+    y = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
+    xin = _in(x, split)
+    rc = native.kernels().die_kern_nhwc_to_nchw_strided(_ptr(xin), _ptr(y), B, H, W, int(C), Cs, _stream(), int(split))
+    _check(rc, "nhwc_to_nchw_f32_strided")
+    return y
+
+
+def bmm_rows(A, Bm, N, K, ldc, live=None, split=False, out=None):
+    """C[b] = A[b][:, :K] @ Bm[b][:K, :N] for A [batch, M, lda], Bm [batch, K, ldb] -> [batch, M, ldc],
+    the columns [N, ldc) written 0."""
+    batch, M, lda = A.shape
+    ldb = Bm.shape[2]
+    if Bm.shape[0] != batch or Bm.shape[1] != K:
+        raise ValueError("Bm must be [batch, K, ldb]")
+    o = _storage(out, (batch, M, ldc), split, A.device)
+    ain, bin_, lv = _in(A, split), _in(Bm, split), _live(live, A.device)
+    rc = native.kernels().die_kern_bmm_rows(_ptr(ain), _ptr(bin_), _ptr(o), batch, M, int(N), int(K), lda, ldb, int(ldc),
+                                            _stream(), _ptr(lv), int(split))
+    _check(rc, "bmm_rows")
+    return _out(o, split)
