@@ -441,6 +441,24 @@ float* die_cpu_run_value(const char* model_path, const float* in, const int64_t*
   }
 }
 
+// The graph inputs of a model as segments of a request (onnx::input_segments), the request's numel
+// (what a DP arena item and a sample buffer hold) and its shape.
+char* die_model_inputs(const char* model_path, char** err) {
+  try {
+    const onnx::Model m = onnx::load_onnx(model_path);
+    Json j = Json::object();
+    j["inputs"] = input_segments_json(onnx::input_segments(m));
+    j["input_numel"] = static_cast<long long>(onnx::input_numel(m));
+    Json shp = Json::array();
+    for (auto d : onnx::request_shape(m)) shp.push_back(static_cast<long long>(d));
+    j["request_shape"] = shp;
+    return dup(j.dump());
+  } catch (const std::exception& e) {
+    set_err(err, e.what());
+    return nullptr;
+  }
+}
+
 char* die_onnx_summary(const char* model_path, char** err) {
   try {
     auto m = onnx::load_onnx(model_path);

@@ -288,6 +288,18 @@ int die_kern_embed_tokens(uint64_t ids, uint64_t table, int ldt, uint64_t pos, u
                                              P<float>(kvis), P<int>(kend), Sp, pad_op, pad_c, pad_neg, pad_trunc));
 }
 
+// The same over packed request rows of ld_in floats with a type-id and a mask segment (kernels.h
+// embed_inputs); types / mask 0 = none, ttab = the type table (types set) or the one type row
+int die_kern_embed_inputs(uint64_t ids, uint64_t types, uint64_t mask, int ld_in, uint64_t table, int ldt, uint64_t pos,
+                          uint64_t ttab, int ldtt, int T, uint64_t out, int B, int Sq, int V, int C, uint64_t stream,
+                          int split, uint64_t kvis, uint64_t kend, int Sp, int pad_op, float pad_c, int pad_neg,
+                          int pad_trunc) {
+  return static_cast<int>(kern::embed_inputs(P<const float>(ids), P<const float>(types), P<const float>(mask), ld_in,
+                                             P<const float>(table), ldt, P<const float>(pos), P<const float>(ttab), ldtt,
+                                             T, P<uint16_t>(out), B, Sq, V, C, S(stream), split, P<float>(kvis),
+                                             P<int>(kend), Sp, pad_op, pad_c, pad_neg, pad_trunc));
+}
+
 // Token pooling + L2 normalisation (kernels.h pool_tokens); kvis / kend 0 = unmasked, ws / counters 0 = none
 int die_kern_pool_tokens(uint64_t x, uint64_t out, uint64_t out_f32, int B, int Sq, int C, int D, uint64_t kvis,
                          uint64_t kend, int Sp, float clip_min, int normalize, float eps, uint64_t stream, uint64_t live,
@@ -527,6 +539,14 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
         e["positions"] = o.shift_off != SIZE_MAX;
         e["token_type"] = o.bias_off != SIZE_MAX;
         e["key_data"] = o.out2 >= 0;
+        if (o.in_ld > 0) {  // several graph inputs: where each segment sits in a request row
+          e["row_pitch"] = o.in_ld;
+          e["ids_offset"] = o.seg_ids;
+          e["types_offset"] = o.seg_types;  // -1: no type input
+          e["type_rows"] = o.type_rows;
+          e["token_type"] = o.bias_off != SIZE_MAX || o.seg_types >= 0;
+          e["mask_offset"] = pad_reads_mask(o) ? o.pad.src : -1;  // -1: the pad test reads the ids
+        }
         if (o.out2 >= 0) {
           static const char* cmp[] = {"equal", "greater", "less"};
           e["pad_op"] = cmp[o.pad.op];
@@ -567,6 +587,7 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
     for (auto d : p.output_shape) out.push_back(static_cast<long long>(d));
     j["input_shape"] = in;
     j["output_shape"] = out;
+    j["inputs"] = input_segments_json(p.inputs);
     return dup(j.dump());
   } catch (const std::exception& e) {
     if (err) *err = dup(e.what());

@@ -972,15 +972,41 @@ CpuExecutor::CpuExecutor(onnx::Model model) : model_(std::move(model)) {
 CpuValuePtr CpuExecutor::run(const CpuValuePtr& input, std::unordered_map<std::string, CpuValuePtr>* trace) {
   if (model_.inputs.empty()) throw std::runtime_error("model has no inputs");
   std::unordered_map<std::string, CpuValuePtr> env;
-  env[model_.inputs[0].name] = input;
   // an input declared INT64 / INT32 (token ids) is fed as floats like any other: truncated here
-  if (!input->is_int && (model_.inputs[0].elem_type == onnx::INT64 || model_.inputs[0].elem_type == onnx::INT32)) {
-    auto ids = std::make_shared<CpuValue>();
-    ids->shape = input->shape;
-    ids->is_int = true;
-    ids->i.resize(input->f.size());
-    for (size_t e = 0; e < input->f.size(); ++e) ids->i[e] = static_cast<int64_t>(input->f[e]);
-    env[model_.inputs[0].name] = ids;
+  auto bind = [&](const onnx::ValueInfo& vi, const CpuValuePtr& v) {
+    env[vi.name] = v;
+    if (!v->is_int && (vi.elem_type == onnx::INT64 || vi.elem_type == onnx::INT32)) {
+      auto ids = std::make_shared<CpuValue>();
+      ids->shape = v->shape;
+      ids->is_int = true;
+      ids->i.resize(v->f.size());
+      for (size_t e = 0; e < v->f.size(); ++e) ids->i[e] = static_cast<int64_t>(v->f[e]);
+      env[vi.name] = ids;
+    }
+  };
+  if (model_.inputs.size() == 1) {
+    bind(model_.inputs[0], input);
+  } else {
+    // several graph inputs: `input` holds, per sample, the elements of every input one after the
+    // other in declaration order (onnx::input_segments); each is cut out and bound by name
+    const std::vector<onnx::InputSegment> segs = onnx::input_segments(model_);
+    const size_t numel = segs.back().offset + segs.back().numel;
+    if (input->is_int || input->shape.empty() || input->shape[0] <= 0 ||
+        input->f.size() != static_cast<size_t>(input->shape[0]) * numel)
+      throw std::runtime_error("cpu executor: a model with " + std::to_string(segs.size()) + " inputs takes [N, " +
+                               std::to_string(numel) + "] floats, every input's elements in declaration order");
+    const size_t N = static_cast<size_t>(input->shape[0]);
+    for (size_t k = 0; k < segs.size(); ++k) {
+      auto v = std::make_shared<CpuValue>();
+      v->shape = model_.inputs[k].dims;
+      if (v->shape.empty()) throw std::runtime_error("cpu executor: input " + segs[k].name + " has no batch dimension");
+      v->shape[0] = static_cast<int64_t>(N);
+      v->f.resize(N * segs[k].numel);
+      for (size_t b = 0; b < N; ++b)
+        std::copy_n(input->f.begin() + static_cast<std::ptrdiff_t>(b * numel + segs[k].offset), segs[k].numel,
+                    v->f.begin() + static_cast<std::ptrdiff_t>(b * segs[k].numel));
+      bind(model_.inputs[k], v);
+    }
   }
   const int64_t opset = model_.opset();
   auto get = [&](const std::string& name) -> const CpuValue* {

@@ -79,9 +79,7 @@ std::string plan_signature(const std::string& path, const EngineOptions& o, int 
 size_t model_input_numel(const std::string& path) {
   onnx::Model m = onnx::load_onnx(path);
   if (m.inputs.empty()) throw std::runtime_error("model has no inputs");
-  size_t n = 1;
-  for (size_t k = 1; k < m.inputs[0].dims.size(); ++k) n *= static_cast<size_t>(std::max<int64_t>(1, m.inputs[0].dims[k]));
-  return n;
+  return onnx::input_numel(m);  // every graph input: a request carries them all
 }
 
 // Text capacity the HIP engine will report (kept in sync with hip_engine.hip).

@@ -131,7 +131,9 @@ class CpuEngine : public Engine {
     shard_id_ = opt.shard_id;
     const auto& m = exec_.model();
     if (m.inputs.empty() || m.outputs.empty()) throw std::runtime_error("model needs at least one input and output");
-    in_shape_ = static_shape(m.inputs[0]);
+    // several inputs: one flat request, every input's elements in declaration order
+    in_shape_ = m.inputs.size() == 1 ? static_shape(m.inputs[0]) : onnx::request_shape(m);
+    segments_ = onnx::input_segments(m);
     out_shape_ = static_shape(m.outputs[0]);
     bool dyn = false;
     for (size_t k = 1; k < m.outputs[0].dims.size(); ++k) dyn |= m.outputs[0].dims[k] <= 0;
@@ -188,6 +190,7 @@ class CpuEngine : public Engine {
     j["batches"] = static_cast<long long>(batches_.load());
     j["images"] = static_cast<long long>(images_.load());
     j["options"] = engine_options_json(opt_);
+    j["inputs"] = input_segments_json(segments_);
     return j;
   }
 
@@ -247,6 +250,7 @@ class CpuEngine : public Engine {
   EngineOptions opt_;
   CpuExecutor exec_;
   std::vector<int64_t> in_shape_, out_shape_;
+  std::vector<onnx::InputSegment> segments_;
   std::unique_ptr<SamplePool> pool_;
   std::thread worker_;
   std::mutex mu_;
@@ -259,6 +263,19 @@ class CpuEngine : public Engine {
 };
 
 }  // namespace
+
+Json input_segments_json(const std::vector<onnx::InputSegment>& segs) {
+  Json a = Json::array();
+  for (const onnx::InputSegment& s : segs) {
+    Json e = Json::object();
+    e["name"] = s.name;
+    e["role"] = s.role;
+    e["offset"] = static_cast<long long>(s.offset);
+    e["numel"] = static_cast<long long>(s.numel);
+    a.push_back(e);
+  }
+  return a;
+}
 
 Json engine_options_json(const EngineOptions& o) {
   Json j = Json::object();

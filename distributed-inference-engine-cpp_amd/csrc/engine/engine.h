@@ -300,6 +300,8 @@ struct EngineOptions {
 // Every option as a JSON object (the /health "engine" document and bench.py echo it, so a run's
 // configuration can be reconstructed from its output).
 Json engine_options_json(const EngineOptions& o);
+// The `inputs` entry of an engine's stats: [{name, role, offset, numel}] (onnx::InputSegment).
+Json input_segments_json(const std::vector<onnx::InputSegment>& segs);
 
 // EngineOptions::efficient_batch policy over a per-batch-size forward-time curve (ms[b], b = 1..
 // max_b; ms[0] unused): with `queued` requests waiting, the batch size to dispatch.  Keeps the whole

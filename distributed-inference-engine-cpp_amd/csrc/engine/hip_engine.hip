@@ -741,12 +741,16 @@ class HipEngine : public Engine {
       if (emb) {
         j["vocab"] = emb->gidx;
         static const char* cmp[] = {"==", ">", "<"};
-        if (emb->out2 >= 0)  // a key is visible where this holds
+        if (pad_reads_mask(*emb))  // ... read from the attention-mask input, not the ids
+          j["pad_compare"] = std::string(emb->pad.truncated ? "trunc(mask input)" : "mask input") +
+                             (emb->pad.negated ? " != 0" : " == 0");
+        else if (emb->out2 >= 0)  // a key is visible where this holds
           j["pad_compare"] = std::string(emb->pad.negated ? "not " : "") + (emb->pad.truncated ? "trunc(id) " : "id ") +
                              cmp[emb->pad.op] + " " + std::to_string(emb->pad.value);
         else j["pad_compare"] = "none";
       }
     }
+    j["inputs"] = input_segments_json(plan_.inputs);  // the graph inputs as segments of a request
     j["precision"] = sp_ ? "fp32" : "bf16";
     j["gflop_per_image"] = plan_.flops_per_sample / 1e9;
     j["arena_mib"] = static_cast<double>(plan_.arena_bytes) / (1 << 20);
@@ -891,6 +895,16 @@ class HipEngine : public Engine {
         }
       }
       std::vector<float> h(in_numel_ * max_batch_, id);
+      if (op.in_ld > 0) {  // several graph inputs: a visible in-range id, mask 1, types 0 in their segments
+        const bool masked = pad_reads_mask(op);
+        if (masked) id = static_cast<float>(std::min(1, op.gidx - 1));  // the test reads the mask, not the ids
+        for (size_t b = 0; b < static_cast<size_t>(max_batch_); ++b) {
+          float* row = h.data() + b * in_numel_;
+          std::fill_n(row, in_numel_, 0.f);
+          std::fill_n(row + op.seg_ids, op.S, id);
+          if (masked) std::fill_n(row + op.pad.src, op.S, 1.f);
+        }
+      }
       HIP_CHECK(hipMemcpy(d_in, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
       return;
     }
@@ -1512,6 +1526,18 @@ class HipEngine : public Engine {
                               op.key_mask ? static_cast<const int*>(buf(op.in5)) : nullptr);
           break;
         case PlanOp::EMBED_TOKENS:
+          if (op.in_ld > 0) {  // several graph inputs: segments of the packed request rows
+            const float* row = static_cast<const float*>(buf(op.in));
+            const bool typed = op.seg_types >= 0;
+            e = kern::embed_inputs(row + op.seg_ids, typed ? row + op.seg_types : nullptr,
+                                   op.pad.src >= 0 && op.out2 >= 0 ? row + op.pad.src : nullptr, op.in_ld, prm(op.w_off),
+                                   op.C, prm(op.shift_off), typed ? prm(op.type_off) : prm(op.bias_off), op.C,
+                                   op.type_rows, static_cast<uint16_t*>(buf(op.out)), B, op.S, op.gidx, op.C, st, sp_,
+                                   static_cast<float*>(buf(op.out2)), static_cast<int*>(buf(op.out3)),
+                                   op.out2 >= 0 ? kern::key_pitch(op.S) : 0, op.pad.op, op.pad.value, op.pad.negated,
+                                   op.pad.truncated);
+            break;
+          }
           e = kern::embed_tokens(static_cast<const float*>(buf(op.in)), prm(op.w_off), op.C, prm(op.shift_off),
                                  prm(op.bias_off), static_cast<uint16_t*>(buf(op.out)), B, op.S, op.gidx, op.C, st, sp_,
                                  static_cast<float*>(buf(op.out2)), static_cast<int*>(buf(op.out3)),

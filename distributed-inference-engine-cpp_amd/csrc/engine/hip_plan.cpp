@@ -70,6 +70,9 @@ struct Val {
   // form, kv_add: masked, i.e. <= -1e4) where the test `pad` holds; kv_rank = 2 [N, S], 3 [N, 1, S],
   // 4 [N, 1, 1, S]
   PadTest pad;
+  // TOKEN_IDS / KEYVIS of a model with several graph inputs: seg = the input's offset in a sample's
+  // request row, in_idx = its place in the declaration order
+  int seg = 0, in_idx = 0;
   int kv_rank = 2;
   bool kv_add = false;
   // KEYVIS for pooling: kv_last = unsqueezed at the LAST axis, [N, S, 1] (kv_rank 3), kv_D > 0 = then
@@ -211,10 +214,12 @@ class Planner {
   //  * rank 2 [N, F] / rank 3 [N, S, F]: rows -> one ROWS_PREP pass (f32 -> bf16 / split, F padded
   //    to a multiple of 8).
   void define_graph_input() {
+    if (m_.inputs.size() > 1) return define_token_inputs();
     const auto& vi = m_.inputs[0];
     const size_t r = vi.dims.size();
     for (size_t k = 1; k < r; ++k)
       if (vi.dims[k] <= 0) throw std::runtime_error("input dims must be static except the batch");
+    plan_.inputs = onnx::input_segments(m_);
     if (r == 2 && token_input(vi.name)) {  // [N, S] token ids: read in place by EMBED_TOKENS, no ROWS_PREP
       Val in;
       in.kind = Val::TOKEN_IDS;
@@ -226,6 +231,7 @@ class Planner {
       plan_.input_numel = static_cast<size_t>(in.H);
       return;
     }
+    plan_.inputs[0].role = "activations";
     if (r == 4) {
       Val in;
       in.kind = Val::GRAPH_IN;
@@ -261,6 +267,109 @@ class Planner {
     define(vi.name, v);
     plan_.input_shape = r == 3 ? std::vector<int64_t>{1, S, F} : std::vector<int64_t>{1, F};
     plan_.input_numel = static_cast<size_t>(S) * F;
+  }
+
+  // How a graph input is used, through Casts: as the indices of a Gather, and / or in any other way
+  // (`mask_like`: every such other use is one a key mask flows through or ends in).
+  struct InputUse {
+    bool gathered = false, other = false, mask_like = true;
+    std::string other_node;
+  };
+  InputUse input_use(const std::string& name) const {
+    static const char* flows[] = {"Not", "Unsqueeze", "Reshape", "Sub", "Mul", "Where", "Expand", "ReduceSum", "Identity"};
+    InputUse u;
+    std::vector<std::string> work{name};
+    for (size_t w = 0; w < work.size(); ++w) {
+      if (graph_outputs_.count(work[w])) u.other = true, u.mask_like = false, u.other_node = "(graph output)";
+      for (int ci : consumers(work[w])) {
+        const Node& c = m_.nodes[ci];
+        if (c.op_type == "Cast") {
+          work.push_back(c.outputs[0]);
+        } else if (c.op_type == "Gather" && c.inputs.size() == 2 && c.in(1) == work[w] && c.in(0) != work[w]) {
+          u.gathered = true;
+        } else {
+          const bool flow = std::any_of(std::begin(flows), std::end(flows), [&](const char* f) { return c.op_type == f; });
+          const bool compare = c.op_type == "Equal" || c.op_type == "Greater" || c.op_type == "Less";
+          if (!u.other) u.other_node = c.op_type + " " + c.name;
+          u.other = u.other || !compare;  // a pad test against a scalar is a use of ids as ids
+          u.mask_like = u.mask_like && flow;
+        }
+      }
+    }
+    return u;
+  }
+
+  // Two or three graph inputs: a token model taking attention_mask and / or token_type_ids next to
+  // its ids.  All are [N, S] with one S, declared FLOAT, INT64 or INT32, in any order; the request
+  // row of a sample is their concatenation in declaration order (onnx::input_segments), read in
+  // place.  Roles come from use: the indices of an embedding Gather (TOKEN_IDS; which of two is the
+  // ids and which the types is decided by declaration order, the lookups are symmetric) or a
+  // visibility value (KEYVIS rooted in the input: visible = value != 0, truncated first for an
+  // integer declaration).  Anything else is rejected here, naming the input.
+  void define_token_inputs() {
+    const size_t K = m_.inputs.size();
+    auto shape_of = [](const onnx::ValueInfo& vi) {
+      std::string s = "[";
+      for (size_t k = 0; k < vi.dims.size(); ++k) s += (k ? ", " : "") + (k == 0 ? std::string("N") : std::to_string(vi.dims[k]));
+      return s + "]";
+    };
+    if (K > 3)
+      throw std::runtime_error("the model has " + std::to_string(K) + " graph inputs (the last one '" + m_.inputs[K - 1].name +
+                               "'): the HIP engine takes at most 3 (token ids, attention mask, token types)");
+    const auto& first = m_.inputs[0];
+    for (const auto& vi : m_.inputs) {
+      if (vi.dims.size() != 2 || vi.dims[1] <= 0)
+        throw std::runtime_error("input '" + vi.name + "' has the shape " + shape_of(vi) + ": with several graph inputs every "
+                                 "one must be [N, S] (token ids, attention mask, token types of a token model)");
+      if (first.dims.size() == 2 && vi.dims[1] != first.dims[1])
+        throw std::runtime_error("input '" + vi.name + "' has the shape " + shape_of(vi) + " but input '" + first.name + "' " +
+                                 shape_of(first) + ": the inputs of a token model share one sequence length S");
+      if (vi.elem_type != onnx::FLOAT && vi.elem_type != onnx::INT64 && vi.elem_type != onnx::INT32)
+        throw std::runtime_error("input '" + vi.name + "' must be declared FLOAT, INT64 or INT32");
+    }
+    const int S = static_cast<int>(first.dims[1]);
+    plan_.inputs = onnx::input_segments(m_);
+    int n_ids = 0, n_mask = 0;
+    std::vector<Val> vals;
+    for (size_t k = 0; k < K; ++k) {
+      const auto& vi = m_.inputs[k];
+      const InputUse u = input_use(vi.name);
+      Val in;
+      in.H = S;
+      in.buf = kBufGraphIn;
+      in.seg = static_cast<int>(plan_.inputs[k].offset);
+      in.in_idx = static_cast<int>(k);
+      in.pad.truncated = vi.elem_type != onnx::FLOAT;
+      if (u.gathered && u.other)
+        throw std::runtime_error("input '" + vi.name + "' is used both as the indices of an embedding Gather and in " +
+                                 u.other_node + ": a graph input is token ids or a mask, not both");
+      if (u.gathered) {
+        in.kind = Val::TOKEN_IDS;
+        ++n_ids;
+      } else if (u.other && u.mask_like) {
+        in.kind = Val::KEYVIS;  // visible where the value is non-zero: not (value == 0)
+        in.pad.op = 0;
+        in.pad.value = 0.f;
+        in.pad.negated = true;
+        in.pad.src = in.seg;
+        plan_.inputs[k].role = "mask";
+        ++n_mask;
+      } else {
+        throw std::runtime_error("input '" + vi.name + "' is neither the indices of an embedding Gather nor an attention mask" +
+                                 (u.other_node.empty() ? " (it has no reader)" : " (read by " + u.other_node + ")") +
+                                 ": the only further graph inputs the HIP engine takes");
+      }
+      vals.push_back(in);
+    }
+    if (n_ids == 0)
+      throw std::runtime_error("input '" + m_.inputs[1].name + "': a second graph input is taken only by token models, and no "
+                               "input of this one indexes an embedding Gather");
+    if (n_ids > 2 || n_mask > 1)
+      throw std::runtime_error("input '" + m_.inputs[K - 1].name + "': at most two inputs index embedding tables (ids, token "
+                               "types) and at most one is a mask");
+    for (size_t k = 0; k < K; ++k) define(m_.inputs[k].name, vals[k]);
+    plan_.input_shape = {1, static_cast<int64_t>(K), S};
+    plan_.input_numel = K * static_cast<size_t>(S);
   }
 
   // BN parameters -> per-channel (scale, shift).
@@ -976,6 +1085,19 @@ class Planner {
     return it != vid_.end() && vals_[it->second].kind == kind ? &vals_[it->second] : nullptr;
   }
 
+  // The token-id value `name` is, or is a Cast to INT64 / INT32 of (a Cast that need not be lowered yet)
+  const Val* ids_behind(std::string name) const {
+    for (int hops = 0; hops < 4; ++hops) {
+      if (const Val* v = val_if(name, Val::TOKEN_IDS)) return v;
+      auto pr = producer_.find(name);
+      if (pr == producer_.end() || m_.nodes[pr->second].op_type != "Cast") return nullptr;
+      const int to = static_cast<int>(m_.nodes[pr->second].get_int("to", onnx::FLOAT));
+      if (to != onnx::INT64 && to != onnx::INT32) return nullptr;
+      name = m_.nodes[pr->second].in(0);
+    }
+    return nullptr;
+  }
+
   // The first EMBED_TOKENS op of the plan also writes the key data (kvis, kend) every key-masked
   // attention reads; one pad test per model.
   int key_op_ = -1;           // index of that op; its out2 / out3 = kvis / kend once a mask uses them
@@ -1008,6 +1130,7 @@ class Planner {
         o.pad.op = op == "Equal" ? 0 : (op == "Greater") == (side == 0) ? 1 : 2;  // c > ids = ids < c
         o.pad.value = c;
         o.pad.truncated = ids->pad.truncated;
+        if (m_.inputs.size() > 1) o.pad.src = ids->seg;  // which of the inputs the test reads
         define(n.outputs[0], o);
         return;
       }
@@ -1038,6 +1161,9 @@ class Planner {
     if (m && !m->kv_add && (op == "Not" || op == "Cast" || op == "Identity")) {
       Val o = *m;
       if (op == "Not") o.pad.negated = !o.pad.negated;
+      // a mask input cast to an integer type: the test reads the truncated value from there on
+      const int to = op == "Cast" ? static_cast<int>(n.get_int("to", onnx::FLOAT)) : 0;
+      if (o.pad.src >= 0 && (to == onnx::INT64 || to == onnx::INT32)) o.pad.truncated = true;
       define(n.outputs[0], o);
       return;
     }
@@ -1122,7 +1248,14 @@ class Planner {
     p.C = Dp;
     p.Cp = D;
     p.w_off = push_f32(padded(t.f, V));
-    // the position Add, then the token-type Add, each the value's only reader
+    const bool multi = m_.inputs.size() > 1;
+    if (multi) {
+      p.in_ld = static_cast<int>(plan_.input_numel);
+      p.seg_ids = ids.seg;
+    }
+    // the position Add, then the token-type Add, each the value's only reader.  With several graph
+    // inputs the Adds come in any order, and the type term is the lookup of another input in its own
+    // table (a sibling Gather read by that Add alone), which joins this op.
     std::string out = n.outputs[0];
     for (int step = 0; step < 2; ++step) {
       const int ci = sole_consumer(out);
@@ -1130,12 +1263,38 @@ class Planner {
       const Node& a = m_.nodes[ci];
       const std::string& cn = a.in(0) == out ? a.in(1) : a.in(0);
       auto ct = m_.initializers.find(cn);
-      if (ct == m_.initializers.end() || !onnx::is_float_type(ct->second.dtype)) break;
+      if (ct == m_.initializers.end()) {
+        auto pg = producer_.find(cn);
+        if (!multi || pg == producer_.end() || done_[pg->second] || p.bias_off != SIZE_MAX || p.seg_types >= 0) break;
+        const Node& g2 = m_.nodes[pg->second];
+        const Val* ids2 = g2.op_type == "Gather" && g2.inputs.size() == 2 && g2.get_int("axis", 0) == 0 ? ids_behind(g2.in(1)) : nullptr;
+        auto t2 = m_.initializers.find(g2.in(0));
+        if (!ids2 || ids2->in_idx == ids.in_idx || t2 == m_.initializers.end() || consumers(cn).size() != 1 ||
+            graph_outputs_.count(cn))
+          break;
+        const onnx::Tensor& tt = t2->second;
+        if (tt.dims.size() != 2 || tt.dims[1] != D || !onnx::is_float_type(tt.dtype) ||
+            static_cast<int64_t>(tt.f.size()) != tt.numel() || tt.numel() == 0)
+          break;
+        p.seg_types = ids2->seg;
+        p.type_rows = static_cast<int>(tt.dims[0]);
+        p.type_off = push_f32(padded(tt.f, p.type_rows));
+        if (ids2->in_idx < ids.in_idx) {  // the earlier-declared input is the ids: swap the two lookups
+          std::swap(p.seg_ids, p.seg_types);
+          std::swap(p.w_off, p.type_off);
+          std::swap(p.gidx, p.type_rows);
+        }
+        done_[pg->second] = true;
+        done_[ci] = true;
+        out = a.outputs[0];
+        continue;
+      }
+      if (!onnx::is_float_type(ct->second.dtype)) break;
       const auto& d = ct->second.dims;
       const bool is_pos = (d.size() == 2 && d[0] == S && d[1] == D) || (d.size() == 3 && d[0] == 1 && d[1] == S && d[2] == D);
       const bool is_type = (d.size() == 1 && d[0] == D) || (d.size() == 3 && d[0] == 1 && d[1] == 1 && d[2] == D);
-      if (step == 0 && is_pos) p.shift_off = push_f32(padded(ct->second.f, S));
-      else if (is_type && p.bias_off == SIZE_MAX) p.bias_off = push_f32(padded(ct->second.f, 1));
+      if ((step == 0 || multi) && is_pos && p.shift_off == SIZE_MAX) p.shift_off = push_f32(padded(ct->second.f, S));
+      else if (is_type && p.bias_off == SIZE_MAX && p.seg_types < 0) p.bias_off = push_f32(padded(ct->second.f, 1));
       else break;
       done_[ci] = true;
       out = a.outputs[0];

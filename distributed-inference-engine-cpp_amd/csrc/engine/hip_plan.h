@@ -36,7 +36,18 @@
 //    attention op's key_mask flag: EMBED_TOKENS writes the per-sample key data once per forward.
 //    Rejected with a report line: key mask + causal, a visibility value used in any other way,
 //    Gather on another axis or from a non-initializer table, mask shapes other than
-//    [N, 1, 1, S].  A second graph input (attention_mask / token_type_ids tensors) is out of scope.
+//    [N, 1, 1, S].
+//  * attention_mask / token_type_ids graph inputs: 2 or 3 rank-2 inputs [N, S] with one S, declared
+//    FLOAT / INT64 / INT32 in any order; a request row is their concatenation in declaration order
+//    and is read in place.  Roles come from use: an input that only indexes Gather(initializer
+//    [V, D], ., axis 0) is ids or types (the earlier-declared of two is the ids), and the two lookups,
+//    summed by Add with each other and the position Add in any order, are one EMBED_TOKENS op (a
+//    constant type row and a type input exclude each other); an input that is a visibility value
+//    roots the key-mask machinery above as the pad test "value != 0" read from the mask segment
+//    (values other than 0 / 1 are outside the contract: non-zero is visible).  Rejected with a
+//    report line naming the input: different S or rank, more than 3 inputs, an input that is
+//    neither, one used both ways, a second input on a model without token ids; a mask input plus a
+//    different ids-derived pad test is two pad tests.  Such a model is never partitioned.
 //  * sentence embedders: the masked mean over the tokens, Mul(rows, m) -> ReduceSum(axis 1) divided by
 //    ReduceSum(m, axis 1) [-> Clip(min) / Max] with m = the same visibility value unsqueezed at the
 //    last axis [-> Expand to [N, S, D]] -> Cast, is one POOL_TOKENS op reading the key data; an L2
@@ -66,12 +77,16 @@ struct PlanBuf {
 
 // The pad test of a token-id model: a key is visible iff ((truncated ? trunc(id) : id) OP value) !=
 // negated, OP = op (0 Equal, 1 Greater, 2 Less) -- the pad_* arguments of kern::embed_tokens.
+// src: what the test reads -- -1 the ids of a single-input model, else the offset in a sample's
+// request row of the input it reads (models with several graph inputs): the attention-mask input
+// (the test is then "value != 0") or, for a test still derived from ids, that ids input.
 struct PadTest {
   int op = 0;
   float value = 0.f;
   bool negated = false, truncated = false;
+  int src = -1;
   bool operator==(const PadTest& o) const {
-    return op == o.op && value == o.value && negated == o.negated && truncated == o.truncated;
+    return op == o.op && value == o.value && negated == o.negated && truncated == o.truncated && src == o.src;
   }
 };
 
@@ -99,7 +114,10 @@ struct PlanOp {
     EMBED_TOKENS,  // token ids (the fp32 graph input [S], in = -2) -> rows: out [S][C] = table[idx(id)] + pos + type
                   // with w_off = table [gidx = V][C] f32, shift_off = pos [S][C], bias_off = type [C] (C = stored
                   // width, Cp = the model's); key data for key-masked attention when out2 >= 0: out2 = kvis
-                  // f32 [kern::key_pitch(S)], out3 = kend (one int), from the pad test `pad`
+                  // f32 [kern::key_pitch(S)], out3 = kend (one int), from the pad test `pad`.
+                  // Several graph inputs (in_ld > 0, kern::embed_inputs): a sample's request row has in_ld
+                  // floats, the ids at seg_ids, the type ids at seg_types (>= 0: type_off = their table
+                  // [type_rows][C] f32, instead of the constant row bias_off), the mask at pad.src
     POOL_TOKENS  // rows in [S][C] (Cp logical columns) -> one vector: out [C] (bf16 / split) or out_f32 [Cp] (the
                  // graph output).  key_mask = 1: the mean over the visible tokens, sum / max(count, count_min),
                  // with in4 / in5 = the EMBED_TOKENS op's kvis / kend; else the mean of all S rows.
@@ -136,6 +154,8 @@ struct PlanOp {
   // EMBED_TOKENS op (kern::attention); combines with a bias table, never with causal
   int key_mask = 0, in4 = -1, in5 = -1;
   PadTest pad;            // EMBED_TOKENS writing key data (out2 >= 0)
+  int in_ld = 0, seg_ids = 0, seg_types = -1, type_rows = 0;  // EMBED_TOKENS of a model with several graph inputs
+  size_t type_off = SIZE_MAX;
   bool normalize = false;  // POOL_TOKENS
   float count_min = 0.f;   // POOL_TOKENS with key_mask: lower bound of the count of visible tokens
   double flops_per_sample = 0;
@@ -163,13 +183,20 @@ struct PlanOp {
   int in3_parts = 0;
 };
 
+// An EMBED_TOKENS op whose key data comes from an attention-mask input (not from an ids input)
+inline bool pad_reads_mask(const PlanOp& o) {
+  return o.out2 >= 0 && o.pad.src >= 0 && o.pad.src != o.seg_ids && o.pad.src != o.seg_types;
+}
+
 struct Plan {
   std::vector<PlanOp> ops;
   std::vector<PlanBuf> bufs;
   std::vector<uint8_t> params;  // host copy of the packed device parameters
   size_t arena_bytes_per_sample = 0;  // sum of per-sample sizes at the chosen offsets (scaled by Bmax)
   size_t arena_bytes = 0;             // for max_batch
-  std::vector<int64_t> input_shape;   // [1, C, H, W]
+  std::vector<int64_t> input_shape;   // [1, C, H, W]; K token inputs [N, S]: [1, K, S]
+  // the graph inputs as segments of a request row, roles as the planner bound them
+  std::vector<onnx::InputSegment> inputs;
   std::vector<int64_t> output_shape;  // [1, ...]
   size_t input_numel = 0, output_numel = 0;
   double flops_per_sample = 0;

@@ -113,6 +113,9 @@ std::vector<int64_t> per_sample(std::vector<int64_t> s) {
 
 std::vector<HybridSegment> hybrid_partition(const onnx::Model& m, int max_batch, bool split) {
   if (m.inputs.empty() || m.outputs.empty()) throw std::runtime_error("model needs an input and an output");
+  if (m.inputs.size() > 1)
+    throw std::runtime_error("hybrid partition: a model with " + std::to_string(m.inputs.size()) +
+                             " graph inputs is never partitioned (it runs whole on the HIP engine or on the CPU executor)");
   // shapes of every value: one batch-1 pass of the CPU executor
   std::vector<int64_t> in_shape = m.inputs[0].dims;
   for (auto& d : in_shape)

@@ -399,6 +399,21 @@ hipError_t embed_tokens(const float* ids, const float* table, int ldt, const flo
                         uint16_t* out, int B, int S, int V, int C, hipStream_t s, int split = 0, float* kvis = nullptr,
                         int* kend = nullptr, int Sp = 0, int pad_op = 0, float pad_c = 0.f, int pad_neg = 1,
                         int pad_trunc = 0);
+// embed_tokens() for requests that carry further [S] inputs next to the ids (attention_mask,
+// token_type_ids): every sample is one packed row of ld_in >= S floats, and ids / types / mask point
+// at their segment of sample 0, so element (b, s) of each is read at [b * ld_in + s].
+//   out[b, s, :] = table[idx(ids, V)] + pos[s] + ttab[idx(types, T)]      (fp32, in that order)
+//  * types (nullable): ids into ttab, [T] rows of pitch ldtt >= C (ldtt % 4 == 0), through the same
+//    k::token_index -- a bad type id clamps, never reads outside the table.  types == nullptr: ttab is
+//    embed_tokens()' one type row [C] (nullable), T / ldtt unused.
+//  * mask (nullable, needs kvis / kend): the pad test of the key data runs on the mask values
+//    instead of the ids.
+// Everything else as embed_tokens().  ld_in < S, types with T <= 0 or without / with a misaligned
+// ttab, kvis without kend: hipErrorInvalidValue, nothing launched.  One launch.
+hipError_t embed_inputs(const float* ids, const float* types, const float* mask, int ld_in, const float* table, int ldt,
+                        const float* pos, const float* ttab, int ldtt, int T, uint16_t* out, int B, int S, int V, int C,
+                        hipStream_t s, int split = 0, float* kvis = nullptr, int* kend = nullptr, int Sp = 0,
+                        int pad_op = 0, float pad_c = 0.f, int pad_neg = 1, int pad_trunc = 0);
 // Token pooling + L2 normalisation of bf16 / split rows x [B][S][C] (C % 8 == 0 stored, D <= C logical
 // columns) -> one vector per sample: out (nullable) bf16 / split [B][C] with the pad columns 0,
 // out_f32 (nullable) [B][D].

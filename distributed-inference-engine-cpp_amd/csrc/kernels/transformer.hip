@@ -262,6 +262,61 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(
   }
 }
 
+// embed_tokens_kernel for models with attention_mask / token_type_ids graph inputs: the request is one
+// packed row of ld_in floats per sample and ids / types / mask point at their segments of sample 0,
+// so element (b, s) of each is at [b * ld_in + s] (ld_in >= S; the single-input kernel's pitch is S).
+//   out[b, s, :] = table[token_index(ids, V)] + pos[s] + ttab[token_index(types, T)]
+// in fp32, in that order; ttab rows have pitch ldtt.  types == nullptr: ttab is the one constant type
+// row (or nullptr), as in embed_tokens_kernel.  A thread reads its id and its type id once, then
+// moves 8 columns of each operand with 16-B loads and stores.
+// Key-data blocks: the pad test runs on mask[b * ld_in + j] when mask != nullptr, else on the ids.
+__global__ __launch_bounds__(256) void embed_inputs_kernel(
+    const float* __restrict__ ids, const float* __restrict__ types, const float* __restrict__ mask, int ld_in,
+    const float* __restrict__ table, int ldt, const float* __restrict__ pos, const float* __restrict__ ttab, int ldtt,
+    int T, uint16_t* __restrict__ out, int B, int S, int V, int C, int split, int eblocks, float* __restrict__ kvis,
+    int* __restrict__ kend, int Sp, int pad_op, float pad_c, int pad_neg, int pad_trunc) {
+  if (static_cast<int>(blockIdx.x) >= eblocks) {
+    const int b = blockIdx.x - eblocks;  // < B by the launch
+    const float* src = (mask ? mask : ids) + static_cast<long long>(b) * ld_in;
+    __shared__ int wmax[4];
+    int last = 0;
+    for (int j = threadIdx.x; j < Sp; j += 256) {
+      const bool vis = j < S && token_visible(src[j], pad_op, pad_c, pad_neg, pad_trunc);
+      kvis[static_cast<long long>(b) * Sp + j] = vis ? 0.f : -INFINITY;
+      if (vis) last = j + 1;  // j ascends per thread
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = last;
+    __syncthreads();
+    if (threadIdx.x == 0) kend[b] = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+    return;
+  }
+  const int CG = C / 8;
+  const long long total = static_cast<long long>(B) * S * CG;
+  const long long plane = static_cast<long long>(B) * S * C;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += static_cast<long long>(eblocks) * 256) {
+    const int cg = static_cast<int>(i % CG);
+    const long long r = i / CG;
+    const int s = static_cast<int>(r % S);
+    const long long at = (r / S) * ld_in + s;  // (b, s) in the packed request rows
+    const float* trow = table + static_cast<long long>(token_index(ids[at], V)) * ldt + cg * 8;
+    const float4 t0 = *reinterpret_cast<const float4*>(trow), t1 = *reinterpret_cast<const float4*>(trow + 4);
+    float v[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+    if (pos) {
+      const float* p = pos + static_cast<long long>(s) * C + cg * 8;
+      const float4 p0 = *reinterpret_cast<const float4*>(p), p1 = *reinterpret_cast<const float4*>(p + 4);
+      v[0] += p0.x, v[1] += p0.y, v[2] += p0.z, v[3] += p0.w, v[4] += p1.x, v[5] += p1.y, v[6] += p1.z, v[7] += p1.w;
+    }
+    if (ttab) {
+      const float* y = ttab + (types ? static_cast<long long>(token_index(types[at], T)) * ldtt : 0ll) + cg * 8;
+      const float4 y0 = *reinterpret_cast<const float4*>(y), y1 = *reinterpret_cast<const float4*>(y + 4);
+      v[0] += y0.x, v[1] += y0.y, v[2] += y0.z, v[3] += y0.w, v[4] += y1.x, v[5] += y1.y, v[6] += y1.z, v[7] += y1.w;
+    }
+    store8v(out + i * 8, plane, split != 0, v);
+  }
+}
+
 // Token pooling and L2 normalisation of rows x [B][S][C] -> one vector per sample (sentence
 // embedders): the mean over the tokens -- with the key data embed_tokens_kernel wrote, over the
 // VISIBLE tokens only, sum / max(count, clip_min) -- then, optionally, v / max(||v||_2, eps) over the
@@ -1005,6 +1060,25 @@ hipError_t embed_tokens(const float* ids, const float* table, int ldt, const flo
   const int eblocks = grid_for(static_cast<long long>(B) * S * (C / 8));
   hipLaunchKernelGGL(embed_tokens_kernel, dim3(eblocks + (kvis ? B : 0)), dim3(256), 0, s, ids, table, ldt, pos, type,
                      out, B, S, V, C, split, eblocks, kvis, kend, Sp, pad_op, pad_c, pad_neg, pad_trunc);
+  return hipGetLastError();
+}
+
+hipError_t embed_inputs(const float* ids, const float* types, const float* mask, int ld_in, const float* table, int ldt,
+                        const float* pos, const float* ttab, int ldtt, int T, uint16_t* out, int B, int S, int V, int C,
+                        hipStream_t s, int split, float* kvis, int* kend, int Sp, int pad_op, float pad_c, int pad_neg,
+                        int pad_trunc) {
+  auto misaligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; };
+  if (B <= 0 || S <= 0 || V <= 0 || C <= 0 || C % 8 || ldt < C || ldt % 4 || !ids || !table || !out || ld_in < S ||
+      misaligned(table) || misaligned(pos) || misaligned(ttab) || misaligned(out))
+    return hipErrorInvalidValue;
+  if (types && (!ttab || T <= 0 || ldtt < C || ldtt % 4)) return hipErrorInvalidValue;
+  if ((kvis == nullptr) != (kend == nullptr)) return hipErrorInvalidValue;
+  if (mask && !kvis) return hipErrorInvalidValue;  // a mask has no other reader
+  if (kvis && (Sp != (S + 31) / 32 * 32 || misaligned(kvis) || pad_op < 0 || pad_op > 2)) return hipErrorInvalidValue;
+  const int eblocks = grid_for(static_cast<long long>(B) * S * (C / 8));
+  hipLaunchKernelGGL(embed_inputs_kernel, dim3(eblocks + (kvis ? B : 0)), dim3(256), 0, s, ids, types, mask, ld_in, table,
+                     ldt, pos, ttab, ldtt, T, out, B, S, V, C, split, eblocks, kvis, kend, Sp, pad_op, pad_c, pad_neg,
+                     pad_trunc);
   return hipGetLastError();
 }
 

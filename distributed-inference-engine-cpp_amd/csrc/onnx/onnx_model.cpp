@@ -1,5 +1,6 @@
 #include "onnx_model.h"
 
+#include <algorithm>
 #include <cstring>
 #include <fstream>
 #include <queue>
@@ -498,6 +499,62 @@ size_t Model::param_bytes_f32() const {
   size_t n = 0;
   for (auto& kv : initializers) n += kv.second.f.size() * 4;
   return n;
+}
+
+std::vector<InputSegment> input_segments(const Model& m) {
+  std::vector<InputSegment> segs;
+  size_t off = 0;
+  bool have_ids = false;
+  for (const ValueInfo& vi : m.inputs) {
+    InputSegment s;
+    s.name = vi.name;
+    s.offset = off;
+    s.numel = 1;
+    for (size_t k = 1; k < vi.dims.size(); ++k) {
+      if (vi.dims[k] <= 0 && m.inputs.size() > 1)
+        throw OnnxError("input " + vi.name + ": dims must be static except the batch");
+      s.numel *= static_cast<size_t>(std::max<int64_t>(1, vi.dims[k]));
+    }
+    off += s.numel;
+    // a Gather index, directly or behind Casts?
+    bool gathered = false;
+    std::vector<std::string> work{vi.name};
+    for (size_t w = 0; w < work.size(); ++w)
+      for (const Node& n : m.nodes) {
+        if (n.op_type == "Cast" && n.in(0) == work[w] && !n.outputs.empty()) work.push_back(n.outputs[0]);
+        if (n.op_type == "Gather" && n.in(1) == work[w]) gathered = true;
+      }
+    if (gathered) {
+      s.role = have_ids ? "types" : "ids";
+      have_ids = true;
+    } else {
+      s.role = m.inputs.size() > 1 && vi.dims.size() == 2 ? "mask" : "activations";
+    }
+    segs.push_back(std::move(s));
+  }
+  return segs;
+}
+
+size_t input_numel(const Model& m) {
+  size_t n = 0;
+  for (const InputSegment& s : input_segments(m)) n += s.numel;
+  return n;
+}
+
+std::vector<int64_t> request_shape(const Model& m) {
+  if (m.inputs.empty()) return {};
+  if (m.inputs.size() == 1) {
+    std::vector<int64_t> s = m.inputs[0].dims;
+    for (auto& d : s)
+      if (d <= 0) d = 1;
+    if (!s.empty()) s[0] = 1;
+    return s;
+  }
+  bool same = true;
+  for (const ValueInfo& vi : m.inputs)
+    same = same && vi.dims.size() == 2 && vi.dims[1] == m.inputs[0].dims[1] && vi.dims[1] > 0;
+  if (same) return {1, static_cast<int64_t>(m.inputs.size()), m.inputs[0].dims[1]};
+  return {1, static_cast<int64_t>(input_numel(m))};
 }
 
 Model parse_onnx(const uint8_t* data, size_t size) {

@@ -89,6 +89,22 @@ struct Model {
   size_t param_bytes_f32() const;
 };
 
+// One graph input as a segment of a request.  A request's numbers are the concatenation of the
+// per-sample elements of every graph input, in declaration order (a model with one input: that
+// input alone).  role, from the input's use in the graph: "ids" (the first input, in declaration
+// order, that indexes a Gather, through Casts), "types" (a later one), "mask" (any other rank-2
+// input of a model with several inputs), "activations" (everything else).
+struct InputSegment {
+  std::string name, role;
+  size_t offset = 0, numel = 0;  // per sample, in elements
+};
+// Throws when a dim other than the batch is not static.
+std::vector<InputSegment> input_segments(const Model& m);
+size_t input_numel(const Model& m);  // the sum over the inputs
+// The request shape with batch 1: input 0's own for one input; [1, K, S] for K inputs that are all
+// [N, S]; [1, input_numel] otherwise.
+std::vector<int64_t> request_shape(const Model& m);
+
 class OnnxError : public std::runtime_error {
  public:
   using std::runtime_error::runtime_error;

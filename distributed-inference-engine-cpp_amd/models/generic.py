@@ -52,6 +52,14 @@ mix a ResNet / ViT never exercises, random weights, written by the in-tree ONNX 
 * `sbert_ids_hf` the `bert_ids_hf` body with the mask left unexpanded ([N, S, 1] on the rows, an [N, 1]
               count) and LpNormalization.
 * `sbert_cls`  the `bert_ids` body, the CLS token, LpNormalization (no mask in the pooling).
+* `bert_hf3`   `bert_ids_hf` as HF exports it: graph inputs input_ids, attention_mask, token_type_ids
+              (INT64), a [2, D] type table, mask[:, None, None, :] -> float -> (1 - m) * finfo.min added
+              to the scores.  `bert_hf3_maskfirst`: the same at 48 tokens with the inputs declared
+              attention_mask, token_type_ids, input_ids.
+* `sbert_hf2`  `sbert_ids_hf`'s body with FLOAT inputs input_ids, attention_mask, fill -10000, and the
+              sentence-transformers pooling (Unsqueeze(-1) -> Expand -> Cast of attention_mask) +
+              F.normalize.  A request of these three is the concatenation of the inputs' [S] in
+              declaration order (`synthetic_request`).
 `synthetic_input(model, batch)` gives inputs of the right shape (token-id models: float32 ids in
 [1, V), sample i padded with 0 past a length that cycles through 1, 32, S, 45, 33, every third sample
 with one interior pad id).  The CPU executor is the fp32
@@ -88,10 +96,18 @@ SPECS = {
     "sbert_ids": dict(seq=48, dim=128, heads=2, ffn=256, layers=2, vocab=1000, pad=0),
     "sbert_ids_hf": dict(seq=160, dim=128, heads=4, ffn=256, layers=2, vocab=1000, pad=0),
     "sbert_cls": dict(seq=48, dim=128, heads=2, ffn=256, layers=2, vocab=1000, pad=0),
+    "bert_hf3": dict(seq=160, dim=128, heads=4, ffn=256, layers=2, classes=3, vocab=1000, pad=0, types=2,
+                     inputs=("ids", "mask", "types"), int_input=True, mask_fill="finfo_min"),
+    "sbert_hf2": dict(seq=160, dim=128, heads=4, ffn=256, layers=2, vocab=1000, pad=0,
+                      inputs=("ids", "mask"), int_input=False, mask_fill=-10000.0),
+    "bert_hf3_maskfirst": dict(seq=48, dim=128, heads=4, ffn=256, layers=2, classes=3, vocab=1000, pad=0, types=2,
+                               inputs=("mask", "types", "ids"), int_input=True, mask_fill="finfo_min"),
 }
 
 MASKED = ("gpt_causal", "bert_relpos", "bert_window", "bert_keymask")
-TOKEN_IDS = ("bert_ids", "bert_ids_hf", "sbert_ids", "sbert_ids_hf", "sbert_cls")
+MULTI_INPUT = ("bert_hf3", "sbert_hf2", "bert_hf3_maskfirst")  # input_ids + attention_mask [+ token_type_ids]
+TOKEN_IDS = ("bert_ids", "bert_ids_hf", "sbert_ids", "sbert_ids_hf", "sbert_cls") + MULTI_INPUT
+INPUT_NAMES = {"ids": "input_ids", "mask": "attention_mask", "types": "token_type_ids"}
 
 
 def _rng(seed):
@@ -298,37 +314,74 @@ def build_masked_encoder(seed: int = 0, opset: int = 17, spec: str = "bert_relpo
     return g.model_proto(opset=opset), dict(g.initializers)
 
 
-def build_token_encoder(seed: int = 0, opset: int = 17, spec: str = "bert_ids",
-                        int_input: bool = False) -> Tuple[bytes, Dict[str, np.ndarray]]:
+def build_token_encoder(seed: int = 0, opset: int = 17, spec: str = "bert_ids", int_input=None,
+                        inputs=None) -> Tuple[bytes, Dict[str, np.ndarray]]:
     """Token-id encoders (`bert_ids`, `bert_ids_hf`): the graph input is [N, S] token ids carried as
     numbers (declared FLOAT, or INT64 with int_input), embedded by a Gather, and the attention mask
     is computed from the ids themselves (pad id 0).  The sentence embedders (`sbert_ids`,
     `sbert_ids_hf`, `sbert_cls`) end in a pooled, L2-normalised vector [N, D] instead of the CLS
-    classifier.  Returns (model bytes, initializers)."""
+    classifier.
+    inputs: the graph inputs in declaration order, out of "ids", "mask", "types" (default: the spec's,
+    ("ids",) for the single-input specs).  With "mask" the attention mask (and the pooling mask of an
+    embedder) comes from an attention_mask input instead of the ids; with "types" the token-type
+    embedding is a lookup of a token_type_ids input in a [T, D] table.  The HF-style specs build
+    either way from the same weights (`bert_hf3` / `sbert_hf2` / `bert_hf3_maskfirst` with
+    inputs=("ids",) are the single-input twins: row 0 of the type table is their type row), so a
+    multi-input model fed mask = ids > 0, types = 0 computes what its twin computes.
+    Returns (model bytes, initializers)."""
     from ..utils.onnx_writer import INT64
 
     s = SPECS[spec]
     rng = _rng(seed)
     S, D, H, F, V = s["seq"], s["dim"], s["heads"], s["ffn"], s["vocab"]
     hd = D // H
-    hf = spec in ("bert_ids_hf", "sbert_ids_hf")
+    hf = spec in ("bert_ids_hf", "sbert_ids_hf") + MULTI_INPUT
+    inputs = tuple(inputs if inputs is not None else s.get("inputs", ("ids",)))
+    if int_input is None:
+        int_input = s.get("int_input", False)
+    if "ids" not in inputs or (len(inputs) > 1 and not hf):
+        raise ValueError("inputs %r: ids are required, mask / types inputs only on the HF-style specs" % (inputs,))
     g = GraphBuilder(name=spec)
-    x = g.input("input_ids", ["N", S], elem_type=INT64) if int_input else g.input("input_ids", ["N", S])
+    ins = {r: (g.input(INPUT_NAMES[r], ["N", S], elem_type=INT64) if int_input else g.input(INPUT_NAMES[r], ["N", S]))
+           for r in inputs}
+    x = ins["ids"]
     ids = x if int_input else g.node("Cast", [x], name="ids_int", to=INT64)
     table = g.init("embeddings.word", (0.5 * rng.standard_normal((V, D))).astype(np.float32))
     h = g.node("Gather", [table, ids], name="embeddings.lookup", axis=0)
     h = g.node("Add", [h, g.init("embeddings.position", (0.5 * rng.standard_normal((1, S, D))).astype(np.float32))],
                name="embeddings.add_position")
     if hf:
-        h = g.node("Add", [h, g.init("embeddings.token_type", (0.5 * rng.standard_normal(D)).astype(np.float32))],
-                   name="embeddings.add_type")
+        type_row = (0.5 * rng.standard_normal(D)).astype(np.float32)
+        if "types" in inputs:  # row 0 = the single-input twin's type row; the others from a stream of their own
+            more = (0.5 * _rng(seed + 5000).standard_normal((s.get("types", 2) - 1, D))).astype(np.float32)
+            ttab = g.init("embeddings.token_type", np.concatenate([type_row[None, :], more], axis=0))
+            tids = ins["types"] if int_input else g.node("Cast", [ins["types"]], name="types_int", to=INT64)
+            h = g.node("Add", [h, g.node("Gather", [ttab, tids], name="embeddings.type_lookup", axis=0)],
+                       name="embeddings.add_type")
+        else:
+            h = g.node("Add", [h, g.init("embeddings.token_type", type_row)], name="embeddings.add_type")
     heads_shape = g.const(np.array([0, 0, H, hd], np.int64), "heads_shape")
     merge_shape = g.const(np.array([0, 0, D], np.int64), "merge_shape")
     sqrt2 = g.const(np.array(1.4142135381698608, np.float32), "sqrt2")
     one = g.const(np.array(1.0, np.float32), "one")
     half = g.const(np.array(0.5, np.float32), "half")
     axes12 = g.const(np.array([1, 2], np.int64), "mask_axes")
-    if hf:  # HF: extended = (1 - mask[:, None, None, :]) * -10000, mask = ids > 0, from the float input
+    fill = s.get("mask_fill", -10000.0)
+    fill = float(np.finfo(np.float32).min) if fill == "finfo_min" else fill
+    mask_in = ins.get("mask")
+    if mask_in is not None and int_input:
+        # current HF exports: mask[:, None, None, :] -> to float -> (1 - m) * finfo.min
+        m = g.node("Unsqueeze", [g.node("Unsqueeze", [mask_in, g.const(np.array([1], np.int64), "mask_axis1")],
+                                        name="mask_unsqueeze1"), g.const(np.array([2], np.int64), "mask_axis2")],
+                   name="extended_mask")
+        m = g.node("Cast", [m], name="extended_mask_f", to=1)
+        key_term = g.node("Mul", [g.node("Sub", [one, m], name="inverted_mask"),
+                                  g.const(np.array(fill, np.float32), "mask_value")], name="additive_mask")
+    elif mask_in is not None:  # a float mask input: no Cast
+        m = g.node("Unsqueeze", [mask_in, axes12], name="extended_mask")
+        key_term = g.node("Mul", [g.node("Sub", [one, m], name="inverted_mask"),
+                                  g.const(np.array(fill, np.float32), "mask_value")], name="additive_mask")
+    elif hf:  # HF: extended = (1 - mask[:, None, None, :]) * -10000, mask = ids > 0, from the float input
         mask_f = g.node("Cast", [g.node("Greater", [x, g.const(np.array(0, np.int64 if int_input else np.float32), "pad_id")],
                                         name="attention_mask")], name="attention_mask_f", to=1)
         m = g.node("Unsqueeze", [mask_f, axes12], name="extended_mask")
@@ -379,7 +432,7 @@ def build_token_encoder(seed: int = 0, opset: int = 17, spec: str = "bert_ids",
         t = g.node("Mul", [g.node("Mul", [m1, t], name=p + "gelu/mul"), half], name=p + "gelu/half")
         h = ln(g.node("Add", [linear(t, p + "output", F, D), h], name=p + "residual2"), p + "ln2")
     if spec.startswith("sbert"):
-        y = _sentence_head(g, spec, h, None if hf else is_pad, mask_f if hf else None)
+        y = _sentence_head(g, spec, h, None if hf else is_pad, mask_f if hf and mask_in is None else None, mask_in)
         g.output(y, ["N", D])
         return g.model_proto(opset=opset), dict(g.initializers)
     cls = g.node("Gather", [h, g.const(np.array(0, np.int64), "cls_index")], name="cls_token", axis=1)
@@ -390,14 +443,16 @@ def build_token_encoder(seed: int = 0, opset: int = 17, spec: str = "bert_ids",
     return g.model_proto(opset=opset), dict(g.initializers)
 
 
-def _sentence_head(g, spec, h, is_pad, mask_f):
-    """The pooling + normalisation tail of the sentence embedders on the last hidden states h [N, S, D]."""
+def _sentence_head(g, spec, h, is_pad, mask_f, mask_in=None):
+    """The pooling + normalisation tail of the sentence embedders on the last hidden states h [N, S, D].
+    mask_in: the attention_mask graph input, which then is the visibility value of the
+    sentence-transformers form."""
     last = g.const(np.array([-1], np.int64), "last_axis")
     tokens = g.const(np.array([1], np.int64), "token_axis")
     if spec == "sbert_cls":  # the CLS token, LpNormalization
         cls = g.node("Gather", [h, g.const(np.array(0, np.int64), "cls_index")], name="cls_token", axis=1)
         return g.node("LpNormalization", [cls], name="normalize", axis=-1, p=2)
-    if spec == "sbert_ids_hf":  # the mask stays [N, S, 1] on the rows; an [N, 1] count; LpNormalization
+    if mask_in is None and mask_f is not None:  # (`sbert_ids_hf`) the mask stays [N, S, 1] on the rows; an [N, 1] count; LpNormalization
         summed = g.node("ReduceSum", [g.node("Mul", [h, g.node("Unsqueeze", [mask_f, last], name="pool_mask")],
                                              name="masked_states"), tokens], name="masked_sum", keepdims=0)
         count = g.node("Clip", [g.node("ReduceSum", [mask_f, tokens], name="visible_count", keepdims=1),
@@ -405,7 +460,7 @@ def _sentence_head(g, spec, h, is_pad, mask_f):
         return g.node("LpNormalization", [g.node("Div", [summed, count], name="mean_pool")], name="normalize", axis=1, p=2)
     # sentence-transformers: mask.unsqueeze(-1).expand(h.size()).float(); sum(h * m, 1) / clamp(m.sum(1), 1e-9);
     # then F.normalize(p=2, dim=1): x / clamp(norm(x), 1e-12).expand_as(x)
-    vis = g.node("Not", [is_pad], name="visible")
+    vis = mask_in if mask_in is not None else g.node("Not", [is_pad], name="visible")
     m = g.node("Expand", [g.node("Unsqueeze", [vis, last], name="pool_mask"), g.node("Shape", [h], name="states_shape")],
                name="pool_mask_expanded")
     m = g.node("Cast", [m], name="pool_mask_f", to=1)
@@ -667,7 +722,10 @@ BUILDERS = {"mlp": build_mlp, "bert": build_bert, "se_cnn": build_se_cnn, "ratio
             "bert_ids_hf": lambda seed=0: build_token_encoder(seed, spec="bert_ids_hf"),
             "sbert_ids": lambda seed=0: build_token_encoder(seed, spec="sbert_ids"),
             "sbert_ids_hf": lambda seed=0: build_token_encoder(seed, spec="sbert_ids_hf"),
-            "sbert_cls": lambda seed=0: build_token_encoder(seed, spec="sbert_cls")}
+            "sbert_cls": lambda seed=0: build_token_encoder(seed, spec="sbert_cls"),
+            "bert_hf3": lambda seed=0: build_token_encoder(seed, spec="bert_hf3"),
+            "sbert_hf2": lambda seed=0: build_token_encoder(seed, spec="sbert_hf2"),
+            "bert_hf3_maskfirst": lambda seed=0: build_token_encoder(seed, spec="bert_hf3_maskfirst")}
 
 
 def build_onnx(name: str, seed: int = 0) -> bytes:
@@ -680,6 +738,8 @@ def input_shape(name: str):
         return (s["in_features"],)
     if name in ("bert", "bert_long", "bert_hd32", "bert_hd128", "token_mixer", "ln_wide", "ln_offset") + MASKED:
         return (s["seq"] * s["dim"],)
+    if name in MULTI_INPUT:  # a request row: every input's [S] in declaration order
+        return (len(s["inputs"]) * s["seq"],)
     if name in TOKEN_IDS:
         return (s["seq"],)
     return (s["in_ch"], s["image"], s["image"])
@@ -687,6 +747,8 @@ def input_shape(name: str):
 
 def synthetic_input(name: str, batch: int, seed: int = 1) -> np.ndarray:
     rng = np.random.default_rng(seed)
+    if name in MULTI_INPUT:
+        return synthetic_request(name, batch, rng)
     if name in TOKEN_IDS:
         return synthetic_ids(name, batch, rng)
     return rng.standard_normal((batch,) + input_shape(name)).astype(np.float32)
@@ -712,3 +774,24 @@ def synthetic_ids(name: str, batch: int, rng, full_length: bool = False) -> np.n
         if i % 3 == 2 and n >= 3:
             ids[i, n // 2] = pad
     return ids
+
+
+def synthetic_request(name: str, batch: int, rng, inputs=None) -> np.ndarray:
+    """float32 request rows [batch, K * S] of a multi-input token model: the segments of `inputs`
+    (default: the spec's declaration order) one after the other.  Built so that only a mask really
+    read from the mask input gives the right answer: sample i is visible up to synthetic_lengths,
+    every third sample has a hole (mask 0 inside its length), the ids in HIDDEN positions are random
+    non-zero ids, every sample of length >= 3 has one VISIBLE token whose id is 0, and the types are 0
+    up to half the length, then 1."""
+    s = SPECS[name]
+    S, V = s["seq"], s["vocab"]
+    seg = dict(ids=rng.integers(1, V, size=(batch, S)).astype(np.float32), mask=np.zeros((batch, S), np.float32),
+               types=np.zeros((batch, S), np.float32))
+    for i, n in enumerate(synthetic_lengths(name, batch)):
+        seg["mask"][i, :n] = 1
+        seg["types"][i, n // 2:n] = 1
+        if i % 3 == 2 and n >= 3:
+            seg["mask"][i, n // 2] = 0
+        if n >= 3:  # position 1 unless the hole sits there (n = 3)
+            seg["ids"][i, 2 if seg["mask"][i, 1] == 0 else 1] = 0
+    return np.concatenate([seg[r] for r in (inputs or s["inputs"])], axis=1)

@@ -100,6 +100,7 @@ def lib() -> C.CDLL:
         sig("die_dp_follower_join", C.c_long, vp, C.c_int)
         sig("die_cpu_run", vp, cp, f32p, i64p, C.c_int, i64p, C.POINTER(C.c_int), errp)
         sig("die_onnx_summary", vp, cp, errp)
+        sig("die_model_inputs", vp, cp, errp)
         sig("die_worker_create", vp, cp, errp)
         sig("die_worker_port", C.c_int, vp)
         sig("die_worker_health", vp, vp)
@@ -443,7 +444,21 @@ class Engine:
             pass
 
 
+def model_inputs(model_path: str) -> Dict[str, Any]:
+    """The graph inputs of a model as segments of a request: {inputs: [{name, role, offset, numel}],
+    input_numel, request_shape}.  A request's numbers are every input's per-sample elements one after
+    the other in declaration order; role is ids / types / mask / activations, from the input's use."""
+    err = _err_box()
+    p = lib().die_model_inputs(model_path.encode(), C.byref(err))
+    if not p:
+        _raise_if(err, "model_inputs")
+    return json.loads(_take_str(p))
+
+
 def cpu_run(model_path: str, x: np.ndarray) -> np.ndarray:
+    """The CPU executor on x: the input tensor of a model with one graph input; for a model with
+    several, [N, input_numel] (or [N, K, S]) holding every input's elements in declaration order,
+    which the executor splits by the declared dims and binds by name."""
     x = np.ascontiguousarray(x, np.float32)
     shape = (C.c_int64 * x.ndim)(*x.shape)
     out_shape = (C.c_int64 * 8)()
@@ -757,6 +772,9 @@ def _sig_kernels():
     L.die_kern_attention_keymask.argtypes = [u64] * 4 + [i] * 8 + [C.c_float, u64, i, u64, i, i, i, u64, u64]
     L.die_kern_embed_tokens.restype = i
     L.die_kern_embed_tokens.argtypes = [u64, u64, i, u64, u64, u64, i, i, i, i, u64, i, u64, u64, i, i, C.c_float, i, i]
+    L.die_kern_embed_inputs.restype = i
+    L.die_kern_embed_inputs.argtypes = [u64, u64, u64, i, u64, i, u64, u64, i, i, u64, i, i, i, i, u64, i, u64, u64, i, i,
+                                        C.c_float, i, i]
     L.die_kern_pool_tokens.restype = i
     L.die_kern_pool_tokens.argtypes = [u64, u64, u64, i, i, i, i, u64, u64, i, C.c_float, i, C.c_float, u64, u64, i,
                                        u64, u64, u64, i]

@@ -382,7 +382,8 @@ def gather_rows(x, idx, split=False):
 _PAD_OPS = {"eq": 0, "gt": 1, "lt": 2}
 
 
-def embed_tokens(ids, table, pos=None, type_row=None, pad_test=None, split=False):
+def embed_tokens(ids, table, pos=None, type_row=None, pad_test=None, split=False, types=None, type_table=None,
+                 mask=None, mask_trunc=False, packed=None):
     """Embedding lookup on token ids carried as numbers: ids [B, S] (any float / int dtype; the kernel
     reads them as fp32), table [V, D] fp32, pos [S, D], type_row [D] ->
     rows[b, s] = table[idx(ids[b, s])] + pos[s] + type_row summed in fp32, with idx = truncate and
@@ -393,9 +394,19 @@ def embed_tokens(ids, table, pos=None, type_row=None, pad_test=None, split=False
     -inf padding and columns >= S; Sp = S rounded up to 32) and kend [B] int32 = 1 + the last
     visible key (0: none); else (rows, None, None).
     A table whose rows are 16-byte aligned with a pitch that is a multiple of 4 and >= Dp is read in
-    place (a row slice of a larger table, say); any other is copied to pitch Dp."""
+    place (a row slice of a larger table, say); any other is copied to pitch Dp.
+    Models with attention_mask / token_type_ids inputs (the embed_inputs entry point; without any of
+    the following the single-input entry point runs as before):
+    types [B, S] + type_table [T, D]: rows += type_table[idx(types[b, s])] (the same clamp against T;
+    the table is read in place under the same rule as `table`); excludes type_row.
+    mask [B, S]: the key data comes from the mask, a key is visible where mask != 0 (mask_trunc: where
+    trunc(mask) != 0, an integer-declared mask input); excludes pad_test.
+    packed = dict(S=, ids=, types=, mask=): `ids` is ONE tensor [B, L] of request rows holding the
+    segments at these element offsets (types / mask: None = absent), read in place with pitch L."""
     import torch
 
+    if types is not None or mask is not None or packed is not None:
+        return _embed_inputs(ids, table, pos, type_row, pad_test, split, types, type_table, mask, mask_trunc, packed)
     B, S = ids.shape
     V, D = table.shape
     Dp = (D + 7) // 8 * 8
@@ -430,6 +441,85 @@ def embed_tokens(ids, table, pos=None, type_row=None, pad_test=None, split=False
         kend = torch.empty((B,), dtype=torch.int32, device=dev)
     rc = native.kernels().die_kern_embed_tokens(_ptr(idf), _ptr(tab), ldt, _ptr(ps), _ptr(ty), _ptr(out), B, S, V, Dp,
                                                 _stream(), int(split), _ptr(kvis), _ptr(kend), Sp, op, float(val), neg, 0)
+    _check(rc, "embed_tokens")
+    return _out(out, split), kvis, kend
+
+
+def _embed_inputs(ids, table, pos, type_row, pad_test, split, types, type_table, mask, mask_trunc, packed):
+    import torch
+
+    dev = table.device
+    if packed is None:  # separate tensors: pack them ids | types | mask
+        B, S = ids.shape
+        parts, packed = [ids], dict(S=S, ids=0, types=None, mask=None)
+        for name, t in (("types", types), ("mask", mask)):
+            if t is not None:
+                packed[name] = S * len(parts)
+                parts.append(t)
+        rows = torch.cat([t.to(device=dev, dtype=torch.float32) for t in parts], dim=1).contiguous()
+    else:
+        rows = ids.to(device=dev, dtype=torch.float32).contiguous()
+        B, S = rows.shape[0], int(packed["S"])
+    L = rows.shape[1]
+    o_ids, o_types, o_mask = packed["ids"], packed.get("types"), packed.get("mask")
+    for off in (o_ids, o_types, o_mask):  # the kernel reads [off, off + S) of every row: keep it inside
+        if off is not None and not (0 <= int(off) and int(off) + S <= L):
+            raise ValueError("embed_tokens: segment offset %r with S = %d outside the request row of %d" % (off, S, L))
+    if (o_types is not None) != (type_table is not None) or (o_types is not None and type_row is not None):
+        raise ValueError("embed_tokens: a type input needs type_table and excludes type_row")
+    if o_mask is not None and pad_test is not None:
+        raise ValueError("embed_tokens: mask excludes pad_test")
+    V, D = table.shape
+    Dp = (D + 7) // 8 * 8
+
+    def padded(t, nrows):
+        if t is None:
+            return None
+        t = t.to(device=dev, dtype=torch.float32).reshape(nrows, D)
+        if Dp == D:
+            return t.contiguous()
+        o = torch.zeros((nrows, Dp), dtype=torch.float32, device=dev)
+        o[:, :D] = t
+        return o
+
+    def in_place(t):
+        if t is None:
+            return None, 0
+        if (t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= Dp and t.stride(0) % 4 == 0
+                and t.data_ptr() % 16 == 0):
+            return t, int(t.stride(0))
+        return padded(t, t.shape[0]), Dp
+
+    tab, ldt = in_place(table)
+    T = 0
+    if type_table is not None:
+        T = type_table.shape[0]
+        ttab, ldtt = in_place(type_table)
+    else:
+        ttab, ldtt = padded(type_row, 1), Dp
+    ps = padded(pos, S)
+    out = torch.empty(((2,) if split else ()) + (B, S, Dp), dtype=torch.bfloat16, device=dev)
+    kvis = kend = None
+    Sp = op = neg = 0
+    val = 0.0
+    if o_mask is not None:
+        op, val, neg = 0, 0.0, 1  # visible = not (mask == 0)
+    elif pad_test is not None:
+        name, val = pad_test if isinstance(pad_test, (tuple, list)) else ("eq", pad_test)
+        op, neg = _PAD_OPS[name], 1
+    if o_mask is not None or pad_test is not None:
+        Sp = (S + 31) // 32 * 32
+        kvis = torch.empty((B, Sp), dtype=torch.float32, device=dev)
+        kend = torch.empty((B,), dtype=torch.int32, device=dev)
+    base = rows.data_ptr()
+
+    def seg(off):
+        return 0 if off is None else base + 4 * int(off)
+
+    rc = native.kernels().die_kern_embed_inputs(seg(o_ids), seg(o_types), seg(o_mask), L, _ptr(tab), ldt, _ptr(ps),
+                                                _ptr(ttab), ldtt, T, _ptr(out), B, S, V, Dp, _stream(), int(split),
+                                                _ptr(kvis), _ptr(kend), Sp, op, float(val), neg,
+                                                int(bool(mask_trunc) and o_mask is not None))
     _check(rc, "embed_tokens")
     return _out(out, split), kvis, kend
 
