@@ -247,6 +247,21 @@ int die_kern_layernorm(uint64_t x, uint64_t y, uint64_t gamma, uint64_t beta, fl
                                                P<const float>(beta), eps, rows, C, S(stream), split, 0, variant));
 }
 
+// layernorm_rows with every argument: Cl logical columns (0 = C), stats 0 = none, rms != 0 = RMSNorm (beta unused)
+int die_kern_layernorm_ex(uint64_t x, uint64_t y, uint64_t gamma, uint64_t beta, float eps, long long rows, int C,
+                          uint64_t stream, int split, int Cl, int variant, uint64_t stats, int rms) {
+  return static_cast<int>(kern::layernorm_rows(P<const uint16_t>(x), P<uint16_t>(y), P<const float>(gamma),
+                                               P<const float>(beta), eps, rows, C, S(stream), split, Cl, variant,
+                                               P<float>(stats), rms));
+}
+
+// Rotary position embedding of head rows (kernels.h rope_rows)
+int die_kern_rope_rows(uint64_t x, uint64_t y, uint64_t cos, uint64_t sin, int B, int Sq, int H, int D, int ldx, int ldy,
+                       uint64_t stream, int split) {
+  return static_cast<int>(kern::rope_rows(P<const uint16_t>(x), P<uint16_t>(y), P<const float>(cos), P<const float>(sin),
+                                          B, Sq, H, D, ldx, ldy, S(stream), split));
+}
+
 int die_kern_tokens(uint64_t patches, uint64_t cls, uint64_t pos, uint64_t out, int B, int S0, int C, uint64_t stream,
                     int split) {
   return static_cast<int>(kern::tokens_assemble(P<const uint16_t>(patches), P<const float>(cls), P<const float>(pos),
@@ -480,8 +495,8 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
       static const char* kinds[] = {"input_prep", "conv", "pool", "gap", "affine", "to_nchw_f32", "bf16_to_f32",
                                     "layernorm", "tokens", "gather_rows", "attention", "stem", "gconv", "softmax",
                                     "rows_prep", "copy_cols", "binary", "unary", "conv_pair", "pad", "where", "resize", "bmm", "gap_fc",
-                                    "embed_tokens", "pool_tokens"};
-      static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::POOL_TOKENS + 1, "one name per PlanOp kind");
+                                    "embed_tokens", "pool_tokens", "rope"};
+      static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::ROPE + 1, "one name per PlanOp kind");
       e["kind"] = kinds[o.kind];
       e["name"] = o.name;
       e["gflop"] = o.flops_per_sample / 1e9;
@@ -563,7 +578,18 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
         e["seq"] = o.S;
         e["dim"] = o.Cp;
       }
-      if (o.kind == PlanOp::LAYERNORM) e["stats_only"] = o.stats_only != 0;
+      if (o.kind == PlanOp::LAYERNORM) {
+        e["stats_only"] = o.stats_only != 0;
+        e["rms"] = o.rms != 0;
+      }
+      if (o.kind == PlanOp::ROPE) {
+        e["heads"] = o.nh;
+        e["head_dim"] = o.hd;
+        e["seq"] = o.S;
+        e["ld_in"] = o.ld[0];
+        e["col"] = o.col[0];
+        e["layout"] = o.gidx ? "nshd" : "nhsd";  // the logical head view the rotation was written on
+      }
       if (o.kind == PlanOp::CONV || o.kind == PlanOp::TOKENS) e["stats_out"] = o.out_stats >= 0;  // writes the partials
       if (o.kind == PlanOp::STEM) {
         e["pool_fused"] = o.is_max != 0;

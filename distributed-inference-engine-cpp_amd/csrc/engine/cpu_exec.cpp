@@ -622,6 +622,39 @@ CpuValuePtr op_layernorm(const Node& n, const CpuValue& x, const CpuValue* scale
   return y;
 }
 
+// RMSNormalization (opset 23) / SimplifiedLayerNormalization (ONNX Runtime's optimiser):
+// y = x / sqrt(mean(x^2) + eps) * scale over the axes from `axis` on; inv_std (nullable) receives
+// 1 / sqrt(mean(x^2) + eps) per row, the second output of the latter.
+CpuValuePtr op_rmsnorm(const Node& n, const CpuValue& x, const CpuValue* scale, CpuValuePtr* inv_std) {
+  const size_t r = x.shape.size();
+  const int64_t axis = norm_axis(n.get_int("axis", -1), r);
+  const float eps = n.get_float("epsilon", 1e-5f);
+  int64_t outer = 1, D = 1;
+  for (int64_t k = 0; k < axis; ++k) outer *= x.shape[k];
+  for (size_t k = axis; k < r; ++k) D *= x.shape[k];
+  auto y = make_f(x.shape);
+  if (inv_std) {
+    std::vector<int64_t> s(x.shape.begin(), x.shape.begin() + axis);
+    s.resize(r, 1);
+    *inv_std = make_f(s);
+  }
+#pragma omp parallel for if (outer > 16)
+  for (int64_t o = 0; o < outer; ++o) {
+    const float* in = x.f.data() + o * D;
+    float* out = y->f.data() + o * D;
+    double sq = 0;
+    for (int64_t d = 0; d < D; ++d) sq += static_cast<double>(in[d]) * in[d];
+    const float inv = static_cast<float>(1.0 / std::sqrt(sq / D + eps));
+    if (inv_std) (*inv_std)->f[o] = inv;
+    for (int64_t d = 0; d < D; ++d) {
+      float v = in[d] * inv;
+      if (scale) v *= scale->f[d % scale->f.size()];
+      out[d] = v;
+    }
+  }
+  return y;
+}
+
 CpuValuePtr op_reduce(const Node& n, const std::vector<const CpuValue*>& in, int64_t opset) {
   const CpuValue& x = *in[0];
   const size_t r = x.shape.size();
@@ -1160,6 +1193,15 @@ CpuValuePtr CpuExecutor::run(const CpuValuePtr& input, std::unordered_map<std::s
       out = op_softmax(n, *in[0], opset);
     } else if (op == "LayerNormalization") {
       out = op_layernorm(n, *in[0], in.size() > 1 ? in[1] : nullptr, in.size() > 2 ? in[2] : nullptr);
+    } else if (op == "RMSNormalization" || op == "SimplifiedLayerNormalization") {
+      if (in[0]->is_int) fail(n, "needs a float input");
+      CpuValuePtr inv_std;
+      const bool second = n.outputs.size() > 1 && !n.outputs[1].empty();
+      out = op_rmsnorm(n, *in[0], in.size() > 1 ? in[1] : nullptr, second ? &inv_std : nullptr);
+      if (second) {
+        env[n.outputs[1]] = inv_std;
+        if (trace) (*trace)[n.outputs[1]] = inv_std;
+      }
     } else if (op == "ReduceMean" || op == "ReduceSum" || op == "ReduceMax" || op == "ReduceL2") {
       out = op_reduce(n, in, opset);
     } else if (op == "LpNormalization") {

@@ -1504,7 +1504,7 @@ class HipEngine : public Engine {
           else
             e = kern::layernorm_rows(static_cast<const uint16_t*>(buf(op.in)), static_cast<uint16_t*>(buf(op.out)),
                                      prm(op.scale_off), prm(op.shift_off), op.eps, op.rows_per_sample * B, op.C, st, sp_,
-                                     op.Cp);
+                                     op.Cp, 0, nullptr, op.rms);
           break;
         case PlanOp::TOKENS:
           e = kern::tokens_assemble(static_cast<const uint16_t*>(buf(op.in)), prm(op.scale_off), prm(op.shift_off),
@@ -1553,6 +1553,10 @@ class HipEngine : public Engine {
                                 op.key_mask ? kern::key_pitch(op.S) : 0, op.count_min, op.normalize, op.eps, st, live, sp_,
                                 side ? ws_side_ : wss_[s % n_exec_], ws_bytes_, side ? counters_side_ : counterss_[s % n_exec_],
                                 kCounters);
+          break;
+        case PlanOp::ROPE:
+          e = kern::rope_rows(static_cast<const uint16_t*>(buf(op.in)) + op.col[0], static_cast<uint16_t*>(buf(op.out)),
+                              prm(op.scale_off), prm(op.shift_off), B, op.S, op.nh, op.hd, op.ld[0], op.C, st, sp_);
           break;
         case PlanOp::GCONV: {
           kern::GConvArgs g;
@@ -1634,8 +1638,8 @@ class HipEngine : public Engine {
     static const char* kinds[] = {"input_prep", "conv", "pool", "gap", "affine", "to_nchw_f32", "bf16_to_f32",
                                   "layernorm", "tokens", "gather_rows", "attention", "stem", "gconv", "softmax",
                                   "rows_prep", "copy_cols", "binary", "unary", "conv_pair", "pad", "where", "resize", "bmm", "gap_fc",
-                                  "embed_tokens", "pool_tokens"};
-    static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::POOL_TOKENS + 1, "one name per PlanOp kind");
+                                  "embed_tokens", "pool_tokens", "rope"};
+    static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::ROPE + 1, "one name per PlanOp kind");
     Json out = Json::object();
     Json ops = Json::array();
     double total = 0;
@@ -1665,6 +1669,7 @@ class HipEngine : public Engine {
         o["masked"] = op.key_mask != 0;
         o["normalize"] = op.normalize;
       }
+      if (op.kind == PlanOp::LAYERNORM) o["rms"] = op.rms != 0;
       total += us[i];
       ops.push_back(o);
     }

@@ -125,7 +125,8 @@ class Planner {
       // its own report line says that the mask must be an initializer
       // (likewise an embedding Gather on token ids whose table came from an unsupported node: it
       // says that the table must be an initializer)
-      if (blocked && !attn_mask_node(n) && !(n.op_type == "Gather" && token_node(n))) {
+      // (and the Mul of a heads view by a rotary table that came from one: the tables must be initializers)
+      if (blocked && !attn_mask_node(n) && !(n.op_type == "Gather" && token_node(n)) && !(n.op_type == "Mul" && rope_anchor(n))) {
         report_.blocked++;
         mark_unknown(n);
         continue;
@@ -393,6 +394,9 @@ class Planner {
     const std::string& op = n.op_type;
     if (token_node(n)) return lower_token_node(idx);
     if (lower_shape_op(idx)) return;
+    if ((op == "Mul" || op == "Slice") && rope_anchor(n)) return lower_rope(idx);
+    if ((op == "Pow" || (op == "Mul" && n.inputs.size() == 2 && n.in(0) == n.in(1))) && rmsnorm_anchor(n)) return lower_rmsnorm(idx);
+    if (op == "RMSNormalization" || op == "SimplifiedLayerNormalization") return lower_layernorm(idx);
     if (op == "Conv") return n.get_int("group", 1) != 1 ? lower_gconv(idx) : lower_conv(idx);
     if (op == "Gemm" || (op == "MatMul" && is_init(n.in(1)))) return lower_gemm(idx);
     if (op == "MatMul") return lower_attn_matmul(idx);
@@ -2146,18 +2150,26 @@ class Planner {
     throw std::runtime_error("Softmax " + n.name + ": only attention scores or the last axis of rows are supported");
   }
 
+  // LayerNormalization, and the single-node RMSNorms RMSNormalization (opset 23) /
+  // SimplifiedLayerNormalization (ONNX Runtime's optimiser): the same row kernel in its rms mode
   void lower_layernorm(int idx) {
     const Node& n = m_.nodes[idx];
+    const bool rms = n.op_type != "LayerNormalization";
     const Val x = val(n.in(0), n);
     if (x.kind != Val::ROWS_BF16 || !dense(x))
-      throw std::runtime_error("LayerNormalization " + n.name + ": input must be dense rows");
+      throw std::runtime_error(n.op_type + " " + n.name + ": input must be dense rows");
     const int64_t axis = n.get_int("axis", -1);
-    if (!(axis == -1 || axis == (x.rank ? x.rank : 2) - 1)) throw std::runtime_error("LayerNormalization: axis must be last");
+    if (!(axis == -1 || axis == (x.rank ? x.rank : 2) - 1))
+      throw std::runtime_error(rms ? n.op_type + " " + n.name + ": axis must be last" : "LayerNormalization: axis must be last");
+    if (rms)
+      for (size_t k = 1; k < n.outputs.size(); ++k)
+        if (!n.outputs[k].empty() && (!consumers(n.outputs[k]).empty() || graph_outputs_.count(n.outputs[k])))
+          throw std::runtime_error(n.op_type + " " + n.name + ": the inv_std_var output must be unused");
     const int Cl = x.logical();
     std::vector<float> g = init(n.in(1), n).f, b(Cl, 0.f);
-    if (n.inputs.size() > 2 && !n.in(2).empty()) b = init(n.in(2), n).f;
+    if (!rms && n.inputs.size() > 2 && !n.in(2).empty()) b = init(n.in(2), n).f;
     if (static_cast<int>(g.size()) != Cl || static_cast<int>(b.size()) != Cl)
-      throw std::runtime_error("LayerNormalization " + n.name + ": scale/bias size mismatch");
+      throw std::runtime_error(n.op_type + " " + n.name + ": scale/bias size mismatch");
     g.resize(x.C, 0.f);  // stored pad columns: written 0 by the kernel
     b.resize(x.C, 0.f);
     PlanOp p;
@@ -2167,6 +2179,7 @@ class Planner {
     p.scale_off = push_f32(g);
     p.shift_off = push_f32(b);
     p.eps = n.get_float("epsilon", 1e-5f);
+    p.rms = rms ? 1 : 0;
     p.C = x.C;
     p.Cp = Cl;
     p.rows_per_sample = static_cast<long long>(x.H) * x.W;
@@ -2174,6 +2187,242 @@ class Planner {
     Val o = x;
     o.buf = p.out;
     define(n.outputs[0], o);
+    add_op(std::move(p));
+  }
+
+  // ---- RMSNorm as torch exports it ------------------------------------------------------------------
+  // Pow(x, 2) / Mul(x, x) -> ReduceMean(-1, keepdims) -> Add(eps) -> Sqrt -> Div(x, .) /
+  // Mul(x, Reciprocal(.)) / Mul(x, Div(1, .)) [-> Mul(weight [C])]  ==> one LAYERNORM op with rms = 1.
+  // The walk reaches the square first, so the chain is anchored there: a square of rows read only by
+  // a ReduceMean that is not the token-axis mean (lower_spatial_reduce) is this pattern or an error.
+  bool rmsnorm_anchor(const Node& n) const {
+    auto xi = vid_.find(n.in(0));
+    if (xi == vid_.end() || vals_[xi->second].kind != Val::ROWS_BF16) return false;
+    const int rm = sole_consumer(n.outputs[0]);
+    if (rm < 0 || m_.nodes[rm].op_type != "ReduceMean") return false;
+    std::vector<int64_t> ax;
+    node_axes(m_.nodes[rm], ax);
+    const Val& x = vals_[xi->second];
+    return !(x.rank == 3 && (ax == std::vector<int64_t>{1} || ax == std::vector<int64_t>{-2}));
+  }
+
+  void lower_rmsnorm(int idx) {
+    const Node& n = m_.nodes[idx];
+    const Val x = val(n.in(0), n);
+    const std::string& xn = n.in(0);
+    auto fail = [&](const std::string& why) {
+      throw std::runtime_error(n.op_type + " " + n.name + ": a square under a ReduceMean is only supported as the head of "
+                               "the decomposed RMSNorm pattern (" + why + ")");
+    };
+    if (n.op_type == "Pow" && !scalar_is(n.in(1), 2.f)) fail("the exponent must be 2");
+    const Node& rm = m_.nodes[sole_consumer(n.outputs[0])];
+    bool ok;
+    const int64_t axis = last_axis_of(rm, m_, ok);
+    if (!ok || !(axis == -1 || axis == (x.rank ? x.rank : 2) - 1))
+      fail("ReduceMean " + rm.name + " must reduce over the last axis with keepdims");
+    if (!dense(x)) fail("input must be dense rows");
+    const int add = sole_consumer(rm.outputs[0]);
+    if (add < 0 || m_.nodes[add].op_type != "Add")
+      fail("the mean of squares " + rm.outputs[0] + " must be read by the Add of eps alone");
+    const std::string& eps_name = other_input(m_.nodes[add], rm.outputs[0]);
+    auto ei = m_.initializers.find(eps_name);
+    if (ei == m_.initializers.end() || ei->second.f.size() != 1)
+      fail("eps of Add " + m_.nodes[add].name + " must be a scalar constant");
+    const int sq_rt = sole_consumer(m_.nodes[add].outputs[0]);
+    if (sq_rt < 0 || m_.nodes[sq_rt].op_type != "Sqrt") fail("no Sqrt of mean + eps");
+    const std::string& rt = m_.nodes[sq_rt].outputs[0];
+    std::vector<int> used = {sole_consumer(n.outputs[0]), add, sq_rt};
+    int c = sole_consumer(rt), norm = -1;
+    if (c >= 0 && m_.nodes[c].op_type == "Div" && m_.nodes[c].in(0) == xn && m_.nodes[c].in(1) == rt) {
+      norm = c;
+    } else if (c >= 0 && (m_.nodes[c].op_type == "Reciprocal" ||
+                          (m_.nodes[c].op_type == "Div" && m_.nodes[c].in(1) == rt && scalar_is(m_.nodes[c].in(0), 1.f)))) {
+      used.push_back(c);
+      const std::string& inv = m_.nodes[c].outputs[0];
+      const int mu = sole_consumer(inv);
+      if (mu >= 0 && m_.nodes[mu].op_type == "Mul" && other_input(m_.nodes[mu], inv) == xn) norm = mu;
+    }
+    if (norm < 0) fail("no x / sqrt, x * Reciprocal(sqrt) or x * (1 / sqrt) after Sqrt " + m_.nodes[sq_rt].name);
+    used.push_back(norm);
+    std::vector<float> g(x.C, 1.f);
+    std::string cur = m_.nodes[norm].outputs[0];
+    c = sole_consumer(cur);
+    if (c >= 0 && m_.nodes[c].op_type == "Mul" && is_init(other_input(m_.nodes[c], cur)) &&
+        static_cast<int>(m_.initializers.at(other_input(m_.nodes[c], cur)).f.size()) == x.logical()) {
+      g = m_.initializers.at(other_input(m_.nodes[c], cur)).f;
+      used.push_back(c);
+      cur = m_.nodes[c].outputs[0];
+    }
+    if (x.padded()) fail("C % 8 == 0 (stored pad columns)");
+    for (int u : used) done_[u] = true;
+    PlanOp p;
+    p.kind = PlanOp::LAYERNORM;
+    p.name = n.name + "+decomposed_rmsnorm";
+    p.in = x.buf;
+    p.scale_off = push_f32(g);
+    p.shift_off = push_f32(std::vector<float>(x.C, 0.f));
+    p.eps = ei->second.f[0];
+    p.rms = 1;
+    p.C = x.C;
+    p.Cp = x.C;
+    p.rows_per_sample = static_cast<long long>(x.H) * x.W;
+    p.out = new_buf(static_cast<size_t>(x.H) * x.W * x.C * 2);
+    Val o = x;
+    o.buf = p.out;
+    o.has_affine = false;
+    define(cur, o);
+    add_op(std::move(p));
+  }
+
+  // ---- rotary position embeddings ---------------------------------------------------------------------
+  // On a heads view x, [N, H, S, hd] (perm {0,2,1,3}) or [N, S, H, hd] (identity), torch's
+  // x * cos + rotate_half(x) * sin exports as Mul(x, COS), Slice(x, 0:hd/2), Slice(x, hd/2:hd), Neg(hi),
+  // Concat([-hi, lo], -1), Mul(., SIN), Add.  A Mul or a last-axis Slice reading such a view is one of
+  // x's three readers in that pattern or an error; the whole pattern is one ROPE op.
+  static int rope_layout(const Val& v) {
+    if (v.kind != Val::HEADS) return -1;
+    if (v.perm == std::array<int, 4>{{0, 2, 1, 3}}) return 0;
+    if (v.perm == std::array<int, 4>{{0, 1, 2, 3}}) return 1;
+    return -1;
+  }
+  // the heads-view operand of a Mul / Slice (-1: none)
+  int rope_operand(const Node& n) const {
+    const int k = n.op_type == "Slice" ? 1 : 2;
+    for (int side = 0; side < k && side < static_cast<int>(n.inputs.size()); ++side) {
+      auto it = vid_.find(n.in(side));
+      if (it != vid_.end() && rope_layout(vals_[it->second]) >= 0) return side;
+    }
+    return -1;
+  }
+  // a Slice of a heads view, or a Mul of one that a Slice reads too (a Mul alone keeps its other lowerings)
+  bool rope_anchor(const Node& n) const {
+    const int side = rope_operand(n);
+    if (side < 0 || n.op_type == "Slice") return side >= 0;
+    for (int c : consumers(n.in(side)))
+      if (m_.nodes[c].op_type == "Slice" && m_.nodes[c].in(0) == n.in(side)) return true;
+    return false;
+  }
+
+  // starts / ends / axes / steps of a one-axis Slice (attributes or inputs); false when not static
+  bool slice_range(const Node& n, int64_t& s0, int64_t& e0, int64_t& axis, int64_t& step) const {
+    std::vector<int64_t> starts = n.get_ints("starts"), ends = n.get_ints("ends"), axes = n.get_ints("axes"), steps;
+    if (starts.empty() && n.inputs.size() >= 3) {
+      if (!ints_of(n.in(1), starts) || !ints_of(n.in(2), ends)) return false;
+      if (n.inputs.size() > 3 && !n.in(3).empty() && !ints_of(n.in(3), axes)) return false;
+      if (n.inputs.size() > 4 && !n.in(4).empty() && !ints_of(n.in(4), steps)) return false;
+    }
+    if (starts.size() != 1 || ends.size() != 1 || axes.size() > 1 || steps.size() > 1) return false;
+    s0 = starts[0];
+    e0 = ends[0];
+    axis = axes.empty() ? 0 : axes[0];
+    step = steps.empty() ? 1 : steps[0];
+    return true;
+  }
+
+  // A rotary table: a float initializer that broadcasts over the view's logical shape as [S][hd]
+  std::vector<float> rope_table(const Node& at, const std::string& name, const Val& x, int layout) const {
+    auto it = m_.initializers.find(name);
+    if (it == m_.initializers.end())
+      throw std::runtime_error("Mul " + at.name + ": the rotary table " + name + " must be an initializer (tables computed "
+                               "in the graph or gathered by a position_ids input are not supported)");
+    const auto& t = it->second;
+    const int64_t S = x.H, hd = x.hd;
+    using V = std::vector<int64_t>;
+    const bool ok = layout == 0 ? (t.dims == V{S, hd} || t.dims == V{1, S, hd} || t.dims == V{1, 1, S, hd})
+                                : t.dims == V{1, S, 1, hd};
+    if (!ok || t.f.size() != static_cast<size_t>(S * hd)) {
+      std::string shp;
+      for (auto d : t.dims) shp += (shp.empty() ? "" : ", ") + std::to_string(d);
+      throw std::runtime_error("Mul " + at.name + ": the rotary table " + name + " [" + shp + "] does not broadcast over the "
+                               "heads as [S, hd] = [" + std::to_string(S) + ", " + std::to_string(hd) + "] (accepted: " +
+                               (layout == 0 ? "[S, hd], [1, S, hd], [1, 1, S, hd]" : "[1, S, 1, hd]") + ")");
+    }
+    return t.f;
+  }
+
+  void lower_rope(int idx) {
+    const Node& n = m_.nodes[idx];
+    const std::string& xn = n.in(rope_operand(n));
+    const Val x = val(xn, n);
+    const int layout = rope_layout(x), hd = x.hd, h2 = x.hd / 2;
+    const std::string where = n.op_type + " " + n.name + ": ";
+    if (graph_outputs_.count(xn)) throw std::runtime_error(where + "a heads view cannot be a graph output");
+    // x's readers in the pattern: the Mul by COS and the two half Slices
+    int mul_cos = -1, lo = -1, hi = -1;
+    for (int c : consumers(xn)) {
+      const Node& q = m_.nodes[c];
+      if (done_[c] && c != idx) continue;
+      if (q.op_type == "Mul" && q.inputs.size() == 2 && q.in(0) != q.in(1)) {
+        if (mul_cos >= 0) throw std::runtime_error(where + "two Muls (" + m_.nodes[mul_cos].name + ", " + q.name + ") read the heads view " + xn + ": not a rotary embedding");
+        mul_cos = c;
+      } else if (q.op_type == "Slice" && q.in(0) == xn) {
+        int64_t s0, e0, axis, step;
+        if (!slice_range(q, s0, e0, axis, step)) throw std::runtime_error("Slice " + q.name + ": the range of a slice of a heads view must be static");
+        if (!(axis == -1 || axis == 3)) throw std::runtime_error("Slice " + q.name + ": a heads view is sliced only along its last axis (rotary embedding)");
+        if (step != 1)
+          throw std::runtime_error("Slice " + q.name + ": step " + std::to_string(step) + " on a heads view: only the rotate-half "
+                                   "rotary embedding (two contiguous halves) is supported, not the interleaved form");
+        if (s0 < 0) s0 += hd;
+        if (e0 < 0) e0 += hd;
+        e0 = std::min<int64_t>(e0, hd);
+        if (s0 == 0 && e0 == h2 && lo < 0) lo = c;
+        else if (s0 == h2 && e0 == hd && hi < 0) hi = c;
+        else
+          throw std::runtime_error("Slice " + q.name + ": [" + std::to_string(s0) + ", " + std::to_string(e0) + ") of a heads view with hd = " +
+                                   std::to_string(hd) + ": the halves of a rotary embedding must be [0, hd/2) and [hd/2, hd) "
+                                   "(partial and interleaved rotary are not supported)");
+      }
+    }
+    if (mul_cos < 0 || lo < 0 || hi < 0)
+      throw std::runtime_error(where + "a Mul / Slice of a heads view is supported only as part of a rotary embedding over all hd "
+                               "columns: Mul(x, COS), Slice(x, 0:hd/2), Slice(x, hd/2:hd) (partial rotary is not supported)");
+    const Node& mc = m_.nodes[mul_cos];
+    const int neg = sole_consumer(m_.nodes[hi].outputs[0]);
+    if (neg < 0 || m_.nodes[neg].op_type != "Neg")
+      throw std::runtime_error("Slice " + m_.nodes[hi].name + ": the high half of a rotary embedding must be read by a Neg alone "
+                               "(partial rotary with a pass-through half is not supported)");
+    const int cat = sole_consumer(m_.nodes[neg].outputs[0]);
+    const int cat2 = sole_consumer(m_.nodes[lo].outputs[0]);
+    if (cat < 0 || cat != cat2 || m_.nodes[cat].op_type != "Concat" || m_.nodes[cat].inputs.size() != 2 ||
+        m_.nodes[cat].in(0) != m_.nodes[neg].outputs[0] || m_.nodes[cat].in(1) != m_.nodes[lo].outputs[0] ||
+        !(m_.nodes[cat].get_int("axis", 0) == -1 || m_.nodes[cat].get_int("axis", 0) == 3))
+      throw std::runtime_error("Slice " + m_.nodes[lo].name + ": the halves of a rotary embedding must meet in Concat([-hi, lo], "
+                               "axis -1)");
+    const int mul_sin = sole_consumer(m_.nodes[cat].outputs[0]);
+    if (mul_sin < 0 || m_.nodes[mul_sin].op_type != "Mul")
+      throw std::runtime_error("Concat " + m_.nodes[cat].name + ": the rotated halves must be multiplied by the SIN table");
+    const Node& ms = m_.nodes[mul_sin];
+    const int add = sole_consumer(ms.outputs[0]);
+    if (add < 0 || add != sole_consumer(mc.outputs[0]) || m_.nodes[add].op_type != "Add" || m_.nodes[add].inputs.size() != 2)
+      throw std::runtime_error("Mul " + ms.name + ": x * COS and rotate_half(x) * SIN must meet in one Add");
+    if (!kern::attention_supported(hd, x.H))
+      throw std::runtime_error(where + "rotary embedding on head dim " + std::to_string(hd) + ": needs a head dim the attention "
+                               "kernel takes (32, 64, 80, 96 or 128)");
+    const std::vector<float> cs = rope_table(mc, other_input(mc, xn), x, layout);
+    const std::vector<float> sn = rope_table(ms, other_input(ms, m_.nodes[cat].outputs[0]), x, layout);
+    for (int u : {mul_cos, lo, hi, neg, cat, mul_sin, add}) done_[u] = true;
+    PlanOp p;
+    p.kind = PlanOp::ROPE;
+    p.name = m_.nodes[add].name + "+rope";
+    p.in = x.buf;
+    p.col[0] = x.col;
+    p.ld[0] = x.pitch();
+    p.S = x.H;
+    p.nh = x.nh;
+    p.hd = hd;
+    p.gidx = layout;
+    p.scale_off = push_f32(cs);
+    p.shift_off = push_f32(sn);
+    p.C = x.nh * hd;
+    p.rows_per_sample = x.H;
+    p.out = new_buf(static_cast<size_t>(x.H) * p.C * 2);
+    Val o = x;  // the same heads view over the new dense rows
+    o.buf = p.out;
+    o.C = p.C;
+    o.cl = 0;
+    o.ld = 0;
+    o.col = 0;
+    define(m_.nodes[add].outputs[0], o);
     add_op(std::move(p));
   }
 

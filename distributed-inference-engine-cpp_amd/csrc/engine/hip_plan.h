@@ -55,6 +55,17 @@
 //    export ReduceL2 -> Clip(min = eps) -> [Expand] -> Div) joins that op when the pooled vector has
 //    no other reader and is a POOL_TOKENS op with S = 1 anywhere else.  As the graph output the op
 //    writes fp32 straight into the output buffer.  Sum / max / last-token pooling: out of scope.
+//  * rotary position embeddings: on a heads view x ([N, H, S, hd] after the head transpose, or
+//    [N, S, H, hd] before it) the seven nodes Mul(x, COS), Slice(x, 0:hd/2), Slice(x, hd/2:hd), Neg,
+//    Concat([-hi, lo]), Mul(., SIN), Add are one ROPE op with the two float initializers as [S][hd]
+//    tables; its output is a heads view on a new dense rows buffer, so the attention lowering is
+//    unchanged (one launch each for Q and K).  Rejected with a report line: halves that do not meet
+//    at hd/2 or a step != 1 (interleaved), rotation of fewer than hd columns (partial), tables that
+//    are not initializers or do not broadcast over [S, hd], a head dim attention does not take.
+//  * RMSNorm: Pow(x, 2) / Mul(x, x) -> ReduceMean(-1) -> Add(eps) -> Sqrt -> Div(x, .) /
+//    Mul(x, Reciprocal(.)) / Mul(x, Div(1, .)) [-> Mul(weight [C])], and the single nodes
+//    RMSNormalization / SimplifiedLayerNormalization, are a LAYERNORM op with rms = 1 (never folded
+//    into its GEMM readers).
 // Anything else falls back to standalone affine/add/relu kernels, or is rejected with a clear
 // error (the CPU executor still runs such models).
 #pragma once
@@ -118,10 +129,13 @@ struct PlanOp {
                   // Several graph inputs (in_ld > 0, kern::embed_inputs): a sample's request row has in_ld
                   // floats, the ids at seg_ids, the type ids at seg_types (>= 0: type_off = their table
                   // [type_rows][C] f32, instead of the constant row bias_off), the mask at pad.src
-    POOL_TOKENS  // rows in [S][C] (Cp logical columns) -> one vector: out [C] (bf16 / split) or out_f32 [Cp] (the
+    POOL_TOKENS,  // rows in [S][C] (Cp logical columns) -> one vector: out [C] (bf16 / split) or out_f32 [Cp] (the
                  // graph output).  key_mask = 1: the mean over the visible tokens, sum / max(count, count_min),
                  // with in4 / in5 = the EMBED_TOKENS op's kvis / kend; else the mean of all S rows.
                  // normalize: then v / max(||v||_2, eps).  S = 1, normalize: a row L2 normalisation
+    ROPE  // rotary position embedding (rotate-half) of the nh heads of hd columns at in [S][ld[0]] + col[0] ->
+          // dense rows out [S][nh*hd]; scale_off / shift_off = the cos / sin tables [S][hd] f32
+          // (kern::rope_rows); gidx = the layout the graph rotated in (0: [N, H, S, hd], 1: [N, S, H, hd])
   } kind;
   std::string name;
   // buffers (-1 = none).  -2 = the graph input (f32 NCHW), -3 = the graph output (f32).
@@ -174,6 +188,7 @@ struct PlanOp {
   // LayerNorm's input, in3 = that statistics buffer, gamma folded into its weights, beta into its
   // bias and colsum_off = the per-column sums of its weights (ConvArgs::row_stats / col_sum).
   int stats_only = 0;
+  int rms = 0;  // LAYERNORM: RMSNorm (no mean, no beta); never folded into its readers
   size_t colsum_off = SIZE_MAX;
   // LayerNorm statistics from the producer's epilogue (stats_from_producer): the CONV that writes a
   // statistics-only LayerNorm's input also writes out_stats = the [M][N/64] (mean, M2) column-group

@@ -200,7 +200,7 @@ void fold_layernorm(Plan& plan) {
       if (b >= 0) readers[b].push_back(i);
   for (int i = 0; i < nops; ++i) {
     PlanOp& p = plan.ops[i];
-    if (p.kind != PlanOp::LAYERNORM || p.stats_only || p.out < 0 || p.in < 0 || p.C != p.Cp || p.join >= 0 ||
+    if (p.kind != PlanOp::LAYERNORM || p.rms || p.stats_only || p.out < 0 || p.in < 0 || p.C != p.Cp || p.join >= 0 ||
         readers[p.out].empty())
       continue;
     bool ok = true;
@@ -265,7 +265,7 @@ void stats_from_producer(Plan& plan) {
   std::vector<bool> drop(nops, false);
   for (int i = 0; i < nops; ++i) {
     PlanOp& p = plan.ops[i];
-    const int w = p.kind == PlanOp::LAYERNORM && p.stats_only && p.in >= 0 ? writer[p.in] : -1;
+    const int w = p.kind == PlanOp::LAYERNORM && !p.rms && p.stats_only && p.in >= 0 ? writer[p.in] : -1;
     if (w >= 0 && p.C == p.Cp && p.C % 64 == 0 && p.C <= 2048 && p.join < 0) {
       PlanOp& q = plan.ops[w];
       const kern::ConvArgs& c = q.conv;

@@ -353,9 +353,23 @@ bool attention_supported(int D, int S, bool masked = false);
 void set_layernorm_xcd(int v);
 // stats != nullptr: statistics mode -- (mean, rstd) of each row to stats[2 row], 2 row + 1 and y is
 // not written (the normalisation is folded into the consuming GEMM: ConvArgs::row_stats).
+// rms != 0: RMSNorm -- the mean is taken as 0, rstd = rsqrt(sum(x^2) / Cl + eps), y = x * rstd * gamma;
+// beta is not read (nullable) and statistics mode writes (0, rstd).
 hipError_t layernorm_rows(const uint16_t* x, uint16_t* y, const float* gamma, const float* beta, float eps,
                           long long rows, int C, hipStream_t s, int split = 0, int Cl = 0, int variant = 0,
-                          float* stats = nullptr);
+                          float* stats = nullptr, int rms = 0);
+// Rotary position embedding (rotate-half) of head rows: x rows [B*S][ldx] with head h at columns
+// [h*D, (h+1)*D) from the pointer (the caller offsets it to the Q or K block of a fused QKV buffer, so
+// ldx may be 3*H*D), y rows [B*S][ldy] in the same head layout, out of place (split: the lo plane
+// B*S*ldx resp. B*S*ldy elements after the hi plane).  cos / sin: fp32 [S][D], full width; with
+// h2 = D / 2 and j < h2, in fp32 on the joined values,
+//   y[j] = x[j] cos[s][j] - x[j + h2] sin[s][j],   y[j + h2] = x[j + h2] cos[s][j + h2] + x[j] sin[s][j + h2]
+// -- what the exported Mul / Slice / Neg / Concat / Mul / Add nodes compute, whatever the tables hold.
+// D: a head dim attention_supported() takes.  One launch, capturable.  An unsupported D, ldx / ldy
+// below H*D or not a multiple of 8, pointers not 16-byte aligned, x and y overlapping:
+// hipErrorInvalidValue, nothing launched.
+hipError_t rope_rows(const uint16_t* x, uint16_t* y, const float* cos, const float* sin, int B, int S, int H, int D,
+                     int ldx, int ldy, hipStream_t s, int split = 0);
 // out[b,0,:] = cls + pos[0]; out[b,1+s,:] = patches[b,s,:] + pos[1+s]   (cls/pos optional, f32)
 // stats (nullable, C % 64 == 0): also the rows' LayerNorm statistics partials, [B*(S0+1)][C/64] float2
 // (mean, M2) as ConvArgs::stats_out writes them

@@ -5,6 +5,8 @@
 // MatMul -> Div -> Softmax -> MatMul attention chain with its Reshape/Transpose views, Concat/Add
 // of the embeddings, Gather of the cls token).  Layouts: activations are bf16 rows [B*S, C] with the
 // head h occupying columns [h*D, (h+1)*D) (no transposes are ever materialised).
+#include <climits>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -47,7 +49,10 @@ __device__ __forceinline__ unsigned xcd_block(unsigned b, unsigned nb, int xcd) 
 // row per wave with 64 x 2 chunks left half the lanes idle in the second round).
 // stats != nullptr: statistics mode -- (mean, rstd) per row to stats[2 row], y is not written (the
 // normalisation is folded into the consuming GEMM, ConvArgs::row_stats).
-template <int CPL, int LPR = 64>
+// RMS: RMSNorm -- the mean is taken as 0, inv = rsqrt(sum(x^2) / Cl + eps), y = x * inv * gamma (b is
+// not read); statistics mode writes (0, inv).  A template parameter, so the LayerNorm instantiations
+// are the code they were.
+template <int CPL, int LPR = 64, bool RMS = false>
 __global__ __launch_bounds__(256) void layernorm_kernel(const uint16_t* __restrict__ x, uint16_t* __restrict__ y,
                                                         const float* __restrict__ g, const float* __restrict__ b,
                                                         float eps, long long rows, int C, int split, int Cl,
@@ -68,8 +73,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const uint16_t* __restri
     if (c < nch) {
       gv[i][0] = *reinterpret_cast<const float4*>(g + c * 8);
       gv[i][1] = *reinterpret_cast<const float4*>(g + c * 8 + 4);
-      bv[i][0] = *reinterpret_cast<const float4*>(b + c * 8);
-      bv[i][1] = *reinterpret_cast<const float4*>(b + c * 8 + 4);
+      if (!RMS) {
+        bv[i][0] = *reinterpret_cast<const float4*>(b + c * 8);
+        bv[i][1] = *reinterpret_cast<const float4*>(b + c * 8 + 4);
+      }
       load8v(xr + c * 8, plane, split != 0, v[i]);
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
@@ -81,7 +88,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const uint16_t* __restri
       for (int t = 0; t < 8; ++t) v[i][t] = 0.f;
     }
   }
-  const float mean = group_sum<LPR>(s) / Cl;
+  const float mean = RMS ? 0.f : group_sum<LPR>(s) / Cl;
   float q2 = 0.f;
 #pragma unroll
   for (int i = 0; i < CPL; ++i)
@@ -102,17 +109,23 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const uint16_t* __restri
     const int c = lane + LPR * i;
     if (c >= nch) continue;
     const float gg[8] = {gv[i][0].x, gv[i][0].y, gv[i][0].z, gv[i][0].w, gv[i][1].x, gv[i][1].y, gv[i][1].z, gv[i][1].w};
-    const float bb[8] = {bv[i][0].x, bv[i][0].y, bv[i][0].z, bv[i][0].w, bv[i][1].x, bv[i][1].y, bv[i][1].z, bv[i][1].w};
     float o[8];
+    if (RMS) {
 #pragma unroll
-    for (int t = 0; t < 8; ++t) o[t] = c * 8 + t < Cl ? (v[i][t] - mean) * inv * gg[t] + bb[t] : 0.f;
+      for (int t = 0; t < 8; ++t) o[t] = c * 8 + t < Cl ? v[i][t] * inv * gg[t] : 0.f;
+    } else {
+      const float bb[8] = {bv[i][0].x, bv[i][0].y, bv[i][0].z, bv[i][0].w, bv[i][1].x, bv[i][1].y, bv[i][1].z, bv[i][1].w};
+#pragma unroll
+      for (int t = 0; t < 8; ++t) o[t] = c * 8 + t < Cl ? (v[i][t] - mean) * inv * gg[t] + bb[t] : 0.f;
+    }
     store8v(y + row * C + c * 8, plane, split != 0, o);
   }
 }
 
 // Rows wider than the register kernels hold (C > 2048): one 256-thread block per row, the row read
 // twice from global / L2 (sum, then squared deviations) and once more for the output; block
-// reductions through LDS.
+// reductions through LDS.  RMS: no mean pass (two reads of the row).
+template <bool RMS = false>
 __global__ __launch_bounds__(256) void layernorm_wide_kernel(const uint16_t* __restrict__ x, uint16_t* __restrict__ y,
                                                              const float* __restrict__ g, const float* __restrict__ b,
                                                              float eps, long long rows, int C, int split, int Cl,
@@ -130,13 +143,14 @@ __global__ __launch_bounds__(256) void layernorm_wide_kernel(const uint16_t* __r
     return red[0] + red[1] + red[2] + red[3];
   };
   float s = 0.f;
-  for (int c = tid; c < nch; c += 256) {
-    float v[8];
-    load8v(xr + c * 8, plane, split != 0, v);
+  if (!RMS)
+    for (int c = tid; c < nch; c += 256) {
+      float v[8];
+      load8v(xr + c * 8, plane, split != 0, v);
 #pragma unroll
-    for (int t = 0; t < 8; ++t) s += c * 8 + t < Cl ? v[t] : 0.f;
-  }
-  const float mean = block_sum(s) / Cl;
+      for (int t = 0; t < 8; ++t) s += c * 8 + t < Cl ? v[t] : 0.f;
+    }
+  const float mean = RMS ? 0.f : block_sum(s) / Cl;
   float q2 = 0.f;
   for (int c = tid; c < nch; c += 256) {
     float v[8];
@@ -155,8 +169,13 @@ __global__ __launch_bounds__(256) void layernorm_wide_kernel(const uint16_t* __r
   for (int c = tid; c < nch; c += 256) {
     float v[8];
     load8v(xr + c * 8, plane, split != 0, v);
+    if (RMS) {
 #pragma unroll
-    for (int t = 0; t < 8; ++t) v[t] = c * 8 + t < Cl ? (v[t] - mean) * inv * g[c * 8 + t] + b[c * 8 + t] : 0.f;
+      for (int t = 0; t < 8; ++t) v[t] = c * 8 + t < Cl ? v[t] * inv * g[c * 8 + t] : 0.f;
+    } else {
+#pragma unroll
+      for (int t = 0; t < 8; ++t) v[t] = c * 8 + t < Cl ? (v[t] - mean) * inv * g[c * 8 + t] + b[c * 8 + t] : 0.f;
+    }
     store8v(y + row * C + c * 8, plane, split != 0, v);
   }
 }
@@ -983,6 +1002,51 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const uint16_t* __res
     for (int c = C + lane; c < ld; c += 64) store1v(y + row * ld + c, plane, sp, 0.f);
 }
 
+// Rotary position embedding on head rows (rotate-half): row r = b * S + s of x holds head h at columns
+// [h*D, (h+1)*D) of pitch ldx; with h2 = D / 2, for j < h2
+//   y[j] = x[j] cos[s][j] - x[j + h2] sin[s][j],   y[j + h2] = x[j + h2] cos[s][j + h2] + x[j] sin[s][j + h2]
+// -- the ONNX x * cos + concat(-x_hi, x_lo) * sin with full-width tables, whatever they hold.  A thread
+// owns one 8-element chunk of the low half and its partner in the high half: two 16-byte loads and
+// two 16-byte stores per plane, the tables as float4; grid-stride over (row, head, chunk).
+__global__ __launch_bounds__(256) void rope_rows_kernel(const uint16_t* __restrict__ x, uint16_t* __restrict__ y,
+                                                        const float* __restrict__ cs, const float* __restrict__ sn,
+                                                        long long rows, int S, int H, int D, int ldx, int ldy,
+                                                        int split) {
+  const int h2 = D / 2, cph = h2 / 8;  // chunks per head half
+  const long long total = rows * H * cph, xplane = rows * ldx, yplane = rows * ldy;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += gridDim.x * 256ll) {
+    const int c = static_cast<int>(i % cph);
+    const long long rh = i / cph;
+    const int h = static_cast<int>(rh % H);
+    const long long row = rh / H;
+    const int sq = static_cast<int>(row % S);
+    const int j = c * 8;
+    const uint16_t* xp = x + row * ldx + h * D + j;
+    float lo[8], hi[8], cl[8], ch[8], sl[8], sh[8];
+    load8v(xp, xplane, split != 0, lo);
+    load8v(xp + h2, xplane, split != 0, hi);
+    const float* cr = cs + static_cast<long long>(sq) * D + j;
+    const float* sr = sn + static_cast<long long>(sq) * D + j;
+    *reinterpret_cast<float4*>(cl) = *reinterpret_cast<const float4*>(cr);
+    *reinterpret_cast<float4*>(cl + 4) = *reinterpret_cast<const float4*>(cr + 4);
+    *reinterpret_cast<float4*>(ch) = *reinterpret_cast<const float4*>(cr + h2);
+    *reinterpret_cast<float4*>(ch + 4) = *reinterpret_cast<const float4*>(cr + h2 + 4);
+    *reinterpret_cast<float4*>(sl) = *reinterpret_cast<const float4*>(sr);
+    *reinterpret_cast<float4*>(sl + 4) = *reinterpret_cast<const float4*>(sr + 4);
+    *reinterpret_cast<float4*>(sh) = *reinterpret_cast<const float4*>(sr + h2);
+    *reinterpret_cast<float4*>(sh + 4) = *reinterpret_cast<const float4*>(sr + h2 + 4);
+    float ol[8], oh[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      ol[t] = lo[t] * cl[t] - hi[t] * sl[t];
+      oh[t] = hi[t] * ch[t] + lo[t] * sh[t];
+    }
+    uint16_t* yp = y + row * ldy + h * D + j;
+    store8v(yp, yplane, split != 0, ol);
+    store8v(yp + h2, yplane, split != 0, oh);
+  }
+}
+
 inline int grid_for(long long work, int cap = 4096) {
   long long g = (work + 255) / 256;
   if (g < 1) g = 1;
@@ -996,37 +1060,64 @@ int g_ln_xcd = 0;  // 1: LayerNorm rows read on the XCD that wrote them (xcd_blo
 }
 void set_layernorm_xcd(int v) { g_ln_xcd = v; }
 
-hipError_t layernorm_rows(const uint16_t* x, uint16_t* y, const float* gamma, const float* beta, float eps,
-                          long long rows, int C, hipStream_t s, int split, int Cl, int variant, float* stats) {
-  if (!stats && !y) return hipErrorInvalidValue;
-  if (C % 8 || Cl < 0 || Cl > C || variant < 0 || variant > 2) return hipErrorInvalidValue;
-  if (Cl == 0) Cl = C;
+namespace {
+template <bool RMS>
+hipError_t layernorm_launch(const uint16_t* x, uint16_t* y, const float* gamma, const float* beta, float eps,
+                            long long rows, int C, hipStream_t s, int split, int Cl, int variant, float* stats) {
   const int blocks = static_cast<int>((rows + 3) / 4);
   if (variant == 1) {
     if (C > 16 * 8 * 6) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((layernorm_kernel<6, 16>), dim3(static_cast<int>((rows + 15) / 16)), dim3(256), 0, s, x, y, gamma,
-                       beta, eps, rows, C, split, Cl, stats, g_ln_xcd);
+    hipLaunchKernelGGL((layernorm_kernel<6, 16, RMS>), dim3(static_cast<int>((rows + 15) / 16)), dim3(256), 0, s, x, y,
+                       gamma, beta, eps, rows, C, split, Cl, stats, g_ln_xcd);
     return hipGetLastError();
   }
   if (variant == 2) {
-    hipLaunchKernelGGL(layernorm_wide_kernel, dim3(static_cast<unsigned>(rows)), dim3(256), 0, s, x, y, gamma, beta, eps,
-                       rows, C, split, Cl, stats, g_ln_xcd);
+    hipLaunchKernelGGL(layernorm_wide_kernel<RMS>, dim3(static_cast<unsigned>(rows)), dim3(256), 0, s, x, y, gamma, beta,
+                       eps, rows, C, split, Cl, stats, g_ln_xcd);
     return hipGetLastError();
   }
   if (C > 512 && C <= 32 * 8 * 3) {  // 513..768 (ViT-B: 768): 32 lanes x 3 chunks, 2 rows per wave
-    hipLaunchKernelGGL((layernorm_kernel<3, 32>), dim3(static_cast<int>((rows + 7) / 8)), dim3(256), 0, s, x, y, gamma,
-                       beta, eps, rows, C, split, Cl, stats, g_ln_xcd);
+    hipLaunchKernelGGL((layernorm_kernel<3, 32, RMS>), dim3(static_cast<int>((rows + 7) / 8)), dim3(256), 0, s, x, y,
+                       gamma, beta, eps, rows, C, split, Cl, stats, g_ln_xcd);
     return hipGetLastError();
   }
   if (C <= 64 * 8)
-    hipLaunchKernelGGL(layernorm_kernel<1>, dim3(blocks), dim3(256), 0, s, x, y, gamma, beta, eps, rows, C, split, Cl, stats, g_ln_xcd);
+    hipLaunchKernelGGL((layernorm_kernel<1, 64, RMS>), dim3(blocks), dim3(256), 0, s, x, y, gamma, beta, eps, rows, C, split, Cl, stats, g_ln_xcd);
   else if (C <= 128 * 8)
-    hipLaunchKernelGGL(layernorm_kernel<2>, dim3(blocks), dim3(256), 0, s, x, y, gamma, beta, eps, rows, C, split, Cl, stats, g_ln_xcd);
+    hipLaunchKernelGGL((layernorm_kernel<2, 64, RMS>), dim3(blocks), dim3(256), 0, s, x, y, gamma, beta, eps, rows, C, split, Cl, stats, g_ln_xcd);
   else if (C <= 256 * 8)
-    hipLaunchKernelGGL(layernorm_kernel<4>, dim3(blocks), dim3(256), 0, s, x, y, gamma, beta, eps, rows, C, split, Cl, stats, g_ln_xcd);
+    hipLaunchKernelGGL((layernorm_kernel<4, 64, RMS>), dim3(blocks), dim3(256), 0, s, x, y, gamma, beta, eps, rows, C, split, Cl, stats, g_ln_xcd);
   else
-    hipLaunchKernelGGL(layernorm_wide_kernel, dim3(static_cast<unsigned>(rows)), dim3(256), 0, s, x, y, gamma, beta, eps,
-                       rows, C, split, Cl, stats, g_ln_xcd);
+    hipLaunchKernelGGL(layernorm_wide_kernel<RMS>, dim3(static_cast<unsigned>(rows)), dim3(256), 0, s, x, y, gamma, beta,
+                       eps, rows, C, split, Cl, stats, g_ln_xcd);
+  return hipGetLastError();
+}
+}  // namespace
+
+hipError_t layernorm_rows(const uint16_t* x, uint16_t* y, const float* gamma, const float* beta, float eps,
+                          long long rows, int C, hipStream_t s, int split, int Cl, int variant, float* stats, int rms) {
+  if (!stats && !y) return hipErrorInvalidValue;
+  if (C % 8 || Cl < 0 || Cl > C || variant < 0 || variant > 2) return hipErrorInvalidValue;
+  if (Cl == 0) Cl = C;
+  return rms ? layernorm_launch<true>(x, y, gamma, beta, eps, rows, C, s, split, Cl, variant, stats)
+             : layernorm_launch<false>(x, y, gamma, beta, eps, rows, C, s, split, Cl, variant, stats);
+}
+
+hipError_t rope_rows(const uint16_t* x, uint16_t* y, const float* cos, const float* sin, int B, int S, int H, int D,
+                     int ldx, int ldy, hipStream_t s, int split) {
+  auto misaligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; };
+  if (B <= 0 || S <= 0 || H <= 0 || !x || !y || !cos || !sin) return hipErrorInvalidValue;
+  if (D != 32 && D != 64 && D != 80 && D != 96 && D != 128) return hipErrorInvalidValue;
+  const long long W = static_cast<long long>(H) * D, rows = static_cast<long long>(B) * S;
+  if (ldx < W || ldy < W || ldx % 8 || ldy % 8 || W > INT_MAX) return hipErrorInvalidValue;
+  if (misaligned(x) || misaligned(y) || misaligned(cos) || misaligned(sin)) return hipErrorInvalidValue;
+  // the element spans the launch touches (both planes in split mode), as half-open address ranges
+  const long long xn = (rows * (split ? 2 : 1) - 1) * ldx + W, yn = (rows * (split ? 2 : 1) - 1) * ldy + W;
+  const uintptr_t xa = reinterpret_cast<uintptr_t>(x), ya = reinterpret_cast<uintptr_t>(y);
+  if (xa < ya + static_cast<uintptr_t>(yn) * 2 && ya < xa + static_cast<uintptr_t>(xn) * 2) return hipErrorInvalidValue;
+  const long long work = rows * H * (D / 16);
+  hipLaunchKernelGGL(rope_rows_kernel, dim3(grid_for(work, 16384)), dim3(256), 0, s, x, y, cos, sin, rows, S, H, D, ldx,
+                     ldy, split);
   return hipGetLastError();
 }
 

@@ -60,6 +60,20 @@ mix a ResNet / ViT never exercises, random weights, written by the in-tree ONNX 
               sentence-transformers pooling (Unsqueeze(-1) -> Expand -> Cast of attention_mask) +
               F.normalize.  A request of these three is the concatenation of the inputs' [S] in
               declaration order (`synthetic_request`).
+* `rope_bert`  the `bert` body (float embeddings in, post-LN, mean pool, 3-class head) with rotary position
+              embeddings on Q and K in the HF layout: on [N, H, S, hd] after the head transpose,
+              x * cos + Concat(Neg(Slice(x, hd/2:)), Slice(x, :hd/2)) * sin with [1, 1, S, hd] tables from
+              theta = 10000.  2 heads of 64, 40 tokens (one full key tile and a partial one).
+* `rope_bert_nshd` the same with the rotation on [N, S, H, hd] before the transposes, tables
+              [1, S, 1, hd]; 2 heads of 128, 24 tokens.
+* `llama_enc`  a token-id embedder shaped like the decoder-derived ones: ids [N, 160] (vocab 1000, pad 0),
+              an embedding Gather with no position table, pre-norm blocks with torch's decomposed RMSNorm
+              (Pow -> ReduceMean -> Add(eps) -> Sqrt -> Div(1, .) -> Mul -> Mul(weight)), bias-free Q / K / V / O
+              projections, RoPE, 4 heads of 32, the ids-derived key mask of `bert_ids_hf`, a SwiGLU MLP
+              (Mul(Mul(g, Sigmoid(g)), u) -> down projection), a final RMSNorm and the `sbert_ids_hf`
+              masked-mean + LpNormalization tail.  Output [N, 128], unit length.
+* `llama_enc_rmsnode` the same body and weights with every RMSNorm written as one RMSNormalization node
+              (opset 23).
 `synthetic_input(model, batch)` gives inputs of the right shape (token-id models: float32 ids in
 [1, V), sample i padded with 0 past a length that cycles through 1, 32, S, 45, 33, every third sample
 with one interior pad id).  The CPU executor is the fp32
@@ -102,11 +116,17 @@ SPECS = {
                       inputs=("ids", "mask"), int_input=False, mask_fill=-10000.0),
     "bert_hf3_maskfirst": dict(seq=48, dim=128, heads=4, ffn=256, layers=2, classes=3, vocab=1000, pad=0, types=2,
                                inputs=("mask", "types", "ids"), int_input=True, mask_fill="finfo_min"),
+    "rope_bert": dict(seq=40, dim=128, heads=2, ffn=256, layers=2, classes=3, theta=10000.0, layout="nhsd"),
+    "rope_bert_nshd": dict(seq=24, dim=256, heads=2, ffn=512, layers=2, classes=3, theta=10000.0, layout="nshd"),
+    "llama_enc": dict(seq=160, dim=128, heads=4, ffn=256, layers=2, vocab=1000, pad=0, theta=10000.0, eps=1e-6),
+    "llama_enc_rmsnode": dict(seq=160, dim=128, heads=4, ffn=256, layers=2, vocab=1000, pad=0, theta=10000.0, eps=1e-6),
 }
 
 MASKED = ("gpt_causal", "bert_relpos", "bert_window", "bert_keymask")
 MULTI_INPUT = ("bert_hf3", "sbert_hf2", "bert_hf3_maskfirst")  # input_ids + attention_mask [+ token_type_ids]
-TOKEN_IDS = ("bert_ids", "bert_ids_hf", "sbert_ids", "sbert_ids_hf", "sbert_cls") + MULTI_INPUT
+ROPE_BERT = ("rope_bert", "rope_bert_nshd")
+LLAMA = ("llama_enc", "llama_enc_rmsnode")
+TOKEN_IDS = ("bert_ids", "bert_ids_hf", "sbert_ids", "sbert_ids_hf", "sbert_cls") + MULTI_INPUT + LLAMA
 INPUT_NAMES = {"ids": "input_ids", "mask": "attention_mask", "types": "token_type_ids"}
 
 
@@ -474,6 +494,174 @@ def _sentence_head(g, spec, h, is_pad, mask_f, mask_in=None):
     return g.node("Div", [pooled, norm], name="normalize")
 
 
+def rope_tables(S: int, hd: int, theta: float = 10000.0):
+    """The rotary tables (cos, sin), float32 [S, hd]: angle[s, j] = s * theta^(-2 (j mod hd/2) / hd), both
+    halves stored (the HF cache layout, emb = cat(freqs, freqs))."""
+    inv = theta ** (-np.arange(0, hd, 2, dtype=np.float64) / hd)
+    ang = np.arange(S, dtype=np.float64)[:, None] * inv[None, :]
+    emb = np.concatenate([ang, ang], axis=1)
+    return np.cos(emb).astype(np.float32), np.sin(emb).astype(np.float32)
+
+
+def rope_nodes(g, x, cos, sin, hd, p, axis=-1, open_end=False, swap=False):
+    """torch's apply_rotary_pos_emb export on the heads view x (last axis hd): x * cos + rotate_half(x) * sin.
+    axis: the Slice / Concat axis as written (-1 or 3); open_end: the high half ends at INT64_MAX (the
+    x[..., hd/2:] export); swap: the operand order of the commutative nodes reversed."""
+    i64 = lambda v, n: g.const(np.array([v], np.int64), n)
+    h2 = hd // 2
+    ax, one = i64(axis, "rope_axis"), i64(1, "rope_step")
+    lo = g.node("Slice", [x, i64(0, "rope_zero"), i64(h2, "rope_half"), ax, one], name=p + "rope/lo")
+    hi = g.node("Slice", [x, i64(h2, "rope_half"), i64(np.iinfo(np.int64).max if open_end else hd, "rope_end"), ax, one],
+                name=p + "rope/hi")
+    rot = g.node("Concat", [g.node("Neg", [hi], name=p + "rope/neg"), lo], name=p + "rope/rotate_half", axis=axis)
+    a = g.node("Mul", [cos, x] if swap else [x, cos], name=p + "rope/cos")
+    b = g.node("Mul", [sin, rot] if swap else [rot, sin], name=p + "rope/sin")
+    return g.node("Add", [b, a] if swap else [a, b], name=p + "rope/add")
+
+
+def build_rope_encoder(seed: int = 0, opset: int = 17, spec: str = "rope_bert") -> Tuple[bytes, Dict[str, np.ndarray]]:
+    """`rope_bert` / `rope_bert_nshd`: the `bert` post-LN encoder with rotary position embeddings on Q
+    and K.  Returns (model bytes, initializers)."""
+    s = SPECS[spec]
+    rng = _rng(seed)
+    S, D, H, F = s["seq"], s["dim"], s["heads"], s["ffn"]
+    hd = D // H
+    nshd = s["layout"] == "nshd"
+    g = GraphBuilder(name=spec)
+    x = g.input("embeddings", ["N", S * D])
+    h = g.node("Reshape", [x, g.const(np.array([0, S, D], np.int64), "seq_shape")], name="to_tokens")
+    heads_shape = g.const(np.array([0, 0, H, hd], np.int64), "heads_shape")
+    merge_shape = g.const(np.array([0, 0, D], np.int64), "merge_shape")
+    sqrt2 = g.const(np.array(1.4142135381698608, np.float32), "sqrt2")
+    one = g.const(np.array(1.0, np.float32), "one")
+    half = g.const(np.array(0.5, np.float32), "half")
+    c, sn = rope_tables(S, hd, s["theta"])
+    tshape = (1, S, 1, hd) if nshd else (1, 1, S, hd)
+    cos, sin = g.init("rope.cos", c.reshape(tshape)), g.init("rope.sin", sn.reshape(tshape))
+
+    def linear(inp, name, fin, fout):
+        w = g.init(name + ".weight", _lin(rng, fin, (fin, fout)))
+        b = g.init(name + ".bias", (0.02 * rng.standard_normal(fout)).astype(np.float32))
+        return g.node("Add", [g.node("MatMul", [inp, w], name=name + "/MatMul"), b], name=name + "/Add")
+
+    def ln(inp, name):
+        gw = g.init(name + ".weight", (1.0 + 0.1 * rng.standard_normal(D)).astype(np.float32))
+        gb = g.init(name + ".bias", (0.1 * rng.standard_normal(D)).astype(np.float32))
+        return g.node("LayerNormalization", [inp, gw, gb], name=name, axis=-1, epsilon=1e-5)
+
+    for i in range(s["layers"]):
+        p = "layer%d." % i
+        q = g.node("Reshape", [linear(h, p + "query", D, D), heads_shape], name=p + "q_heads")
+        k = g.node("Reshape", [linear(h, p + "key", D, D), heads_shape], name=p + "k_heads")
+        v = g.node("Reshape", [linear(h, p + "value", D, D), heads_shape], name=p + "v_heads")
+        if nshd:  # rotate [N, S, H, hd], then transpose
+            q = g.node("Transpose", [rope_nodes(g, q, cos, sin, hd, p + "q_", axis=3, open_end=True)], name=p + "q_perm",
+                       perm=[0, 2, 1, 3])
+            k = g.node("Transpose", [rope_nodes(g, k, cos, sin, hd, p + "k_", axis=3, swap=True)], name=p + "k_perm",
+                       perm=[0, 2, 3, 1])
+        else:  # HF: transpose to [N, H, S, hd], rotate, K transposed again for Q K^T
+            q = rope_nodes(g, g.node("Transpose", [q], name=p + "q_perm", perm=[0, 2, 1, 3]), cos, sin, hd, p + "q_")
+            k = rope_nodes(g, g.node("Transpose", [k], name=p + "k_perm", perm=[0, 2, 1, 3]), cos, sin, hd, p + "k_",
+                           open_end=True, swap=True)
+            k = g.node("Transpose", [k], name=p + "k_t", perm=[0, 1, 3, 2])
+        v = g.node("Transpose", [v], name=p + "v_perm", perm=[0, 2, 1, 3])
+        sc = g.node("Div", [g.node("MatMul", [q, k], name=p + "scores"),
+                            g.const(np.array(math.sqrt(hd), np.float32), "sqrt_d")], name=p + "scale")
+        sc = g.node("Softmax", [sc], name=p + "softmax", axis=-1)
+        ctx = g.node("MatMul", [sc, v], name=p + "context")
+        ctx = g.node("Reshape", [g.node("Transpose", [ctx], name=p + "ctx_perm", perm=[0, 2, 1, 3]), merge_shape],
+                     name=p + "ctx_merge")
+        h = ln(g.node("Add", [linear(ctx, p + "attn_out", D, D), h], name=p + "residual1"), p + "ln1")
+        m = linear(h, p + "intermediate", D, F)
+        t = g.node("Div", [m, sqrt2], name=p + "gelu/div")
+        t = g.node("Add", [g.node("Erf", [t], name=p + "gelu/erf"), one], name=p + "gelu/add")
+        t = g.node("Mul", [g.node("Mul", [m, t], name=p + "gelu/mul"), half], name=p + "gelu/half")
+        h = ln(g.node("Add", [linear(t, p + "output", F, D), h], name=p + "residual2"), p + "ln2")
+    pooled = g.node("ReduceMean", [h], name="mean_pool", axes=[1], keepdims=0)
+    w = g.init("classifier.weight", _lin(rng, D, (s["classes"], D)))
+    b = g.init("classifier.bias", (0.1 * rng.standard_normal(s["classes"])).astype(np.float32))
+    y = g.node("Gemm", [pooled, w, b], name="classifier", transB=1)
+    g.output(y, ["N", s["classes"]])
+    return g.model_proto(opset=opset), dict(g.initializers)
+
+
+def build_llama_encoder(seed: int = 0, opset: int = 17, spec: str = "llama_enc") -> Tuple[bytes, Dict[str, np.ndarray]]:
+    """`llama_enc` / `llama_enc_rmsnode`: a decoder-derived token-id embedder (RMSNorm, RoPE, bias-free
+    projections, SwiGLU, masked mean + L2 normalisation).  Both specs draw the same weights; the
+    second writes each RMSNorm as one RMSNormalization node and needs opset 23.
+    Returns (model bytes, initializers)."""
+    from ..utils.onnx_writer import INT64
+
+    s = SPECS[spec]
+    rng = _rng(seed)
+    S, D, H, F, V = s["seq"], s["dim"], s["heads"], s["ffn"], s["vocab"]
+    hd = D // H
+    node_form = spec == "llama_enc_rmsnode"
+    if node_form:
+        opset = max(opset, 23)
+    g = GraphBuilder(name=spec)
+    x = g.input("input_ids", ["N", S])
+    ids = g.node("Cast", [x], name="ids_int", to=INT64)
+    table = g.init("embed_tokens.weight", (0.5 * rng.standard_normal((V, D))).astype(np.float32))
+    h = g.node("Gather", [table, ids], name="embed_tokens", axis=0)
+    heads_shape = g.const(np.array([0, 0, H, hd], np.int64), "heads_shape")
+    merge_shape = g.const(np.array([0, 0, D], np.int64), "merge_shape")
+    one = g.const(np.array(1.0, np.float32), "one")
+    two = g.const(np.array(2.0, np.float32), "two")
+    eps = g.const(np.array(s["eps"], np.float32), "rms_eps")
+    last = g.const(np.array([-1], np.int64), "rms_axis")
+    c, sn = rope_tables(S, hd, s["theta"])
+    cos, sin = g.init("rope.cos", c.reshape(1, 1, S, hd)), g.init("rope.sin", sn.reshape(1, 1, S, hd))
+    # HF: extended = (1 - mask[:, None, None, :]) * -10000 with mask = ids > 0
+    mask_f = g.node("Cast", [g.node("Greater", [x, g.const(np.array(0, np.float32), "pad_id")], name="attention_mask")],
+                    name="attention_mask_f", to=1)
+    m = g.node("Unsqueeze", [mask_f, g.const(np.array([1, 2], np.int64), "mask_axes")], name="extended_mask")
+    key_term = g.node("Mul", [g.node("Sub", [one, m], name="inverted_mask"),
+                              g.const(np.array(-10000.0, np.float32), "mask_value")], name="additive_mask")
+
+    def proj(inp, name, fin, fout):
+        return g.node("MatMul", [inp, g.init(name + ".weight", _lin(rng, fin, (fin, fout)))], name=name)
+
+    def rms(inp, name):
+        w = g.init(name + ".weight", (1.0 + 0.1 * rng.standard_normal(D)).astype(np.float32))
+        if node_form:
+            return g.node("RMSNormalization", [inp, w], name=name, axis=-1, epsilon=s["eps"])
+        var = g.node("ReduceMean", [g.node("Pow", [inp, two], name=name + "/pow"), last], name=name + "/mean", keepdims=1) \
+            if opset >= 18 else g.node("ReduceMean", [g.node("Pow", [inp, two], name=name + "/pow")], name=name + "/mean",
+                                       axes=[-1], keepdims=1)
+        inv = g.node("Div", [one, g.node("Sqrt", [g.node("Add", [var, eps], name=name + "/add_eps")], name=name + "/sqrt")],
+                     name=name + "/rsqrt")
+        return g.node("Mul", [w, g.node("Mul", [inp, inv], name=name + "/normalize")], name=name + "/scale")
+
+    for i in range(s["layers"]):
+        p = "layer%d." % i
+        a = rms(h, p + "input_norm")
+        q = g.node("Transpose", [g.node("Reshape", [proj(a, p + "q_proj", D, D), heads_shape], name=p + "q_heads")],
+                   name=p + "q_perm", perm=[0, 2, 1, 3])
+        k = g.node("Transpose", [g.node("Reshape", [proj(a, p + "k_proj", D, D), heads_shape], name=p + "k_heads")],
+                   name=p + "k_perm", perm=[0, 2, 1, 3])
+        v = g.node("Transpose", [g.node("Reshape", [proj(a, p + "v_proj", D, D), heads_shape], name=p + "v_heads")],
+                   name=p + "v_perm", perm=[0, 2, 1, 3])
+        q = rope_nodes(g, q, cos, sin, hd, p + "q_", open_end=True)
+        k = g.node("Transpose", [rope_nodes(g, k, cos, sin, hd, p + "k_", open_end=True)], name=p + "k_t", perm=[0, 1, 3, 2])
+        sc = g.node("Div", [g.node("MatMul", [q, k], name=p + "scores"),
+                            g.const(np.array(math.sqrt(hd), np.float32), "sqrt_d")], name=p + "scale")
+        sc = g.node("Softmax", [g.node("Add", [sc, key_term], name=p + "mask/Add")], name=p + "softmax", axis=-1)
+        ctx = g.node("MatMul", [sc, v], name=p + "context")
+        ctx = g.node("Reshape", [g.node("Transpose", [ctx], name=p + "ctx_perm", perm=[0, 2, 1, 3]), merge_shape],
+                     name=p + "ctx_merge")
+        h = g.node("Add", [h, proj(ctx, p + "o_proj", D, D)], name=p + "residual1")
+        a = rms(h, p + "post_attention_norm")
+        gate, up = proj(a, p + "gate_proj", D, F), proj(a, p + "up_proj", D, F)
+        act = g.node("Mul", [g.node("Mul", [gate, g.node("Sigmoid", [gate], name=p + "silu/sigmoid")], name=p + "silu"), up],
+                     name=p + "swiglu")
+        h = g.node("Add", [h, proj(act, p + "down_proj", F, D)], name=p + "residual2")
+    h = rms(h, "norm")
+    y = _sentence_head(g, "sbert_ids_hf", h, None, mask_f)
+    g.output(y, ["N", D])
+    return g.model_proto(opset=opset), dict(g.initializers)
+
+
 def build_se_cnn(seed: int = 0, opset: int = 13) -> Tuple[bytes, Dict[str, np.ndarray]]:
     s = SPECS["se_cnn"]
     rng = _rng(seed)
@@ -725,7 +913,11 @@ BUILDERS = {"mlp": build_mlp, "bert": build_bert, "se_cnn": build_se_cnn, "ratio
             "sbert_cls": lambda seed=0: build_token_encoder(seed, spec="sbert_cls"),
             "bert_hf3": lambda seed=0: build_token_encoder(seed, spec="bert_hf3"),
             "sbert_hf2": lambda seed=0: build_token_encoder(seed, spec="sbert_hf2"),
-            "bert_hf3_maskfirst": lambda seed=0: build_token_encoder(seed, spec="bert_hf3_maskfirst")}
+            "bert_hf3_maskfirst": lambda seed=0: build_token_encoder(seed, spec="bert_hf3_maskfirst"),
+            "rope_bert": lambda seed=0: build_rope_encoder(seed, spec="rope_bert"),
+            "rope_bert_nshd": lambda seed=0: build_rope_encoder(seed, spec="rope_bert_nshd"),
+            "llama_enc": lambda seed=0: build_llama_encoder(seed, spec="llama_enc"),
+            "llama_enc_rmsnode": lambda seed=0: build_llama_encoder(seed, spec="llama_enc_rmsnode")}
 
 
 def build_onnx(name: str, seed: int = 0) -> bytes:
@@ -736,7 +928,7 @@ def input_shape(name: str):
     s = SPECS[name]
     if name in ("mlp", "ratio_mlp"):
         return (s["in_features"],)
-    if name in ("bert", "bert_long", "bert_hd32", "bert_hd128", "token_mixer", "ln_wide", "ln_offset") + MASKED:
+    if name in ("bert", "bert_long", "bert_hd32", "bert_hd128", "token_mixer", "ln_wide", "ln_offset") + MASKED + ROPE_BERT:
         return (s["seq"] * s["dim"],)
     if name in MULTI_INPUT:  # a request row: every input's [S] in declaration order
         return (len(s["inputs"]) * s["seq"],)

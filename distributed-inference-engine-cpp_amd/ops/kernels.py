@@ -355,6 +355,48 @@ def layernorm(x, gamma, beta, eps=1e-5, split=False, variant=0):
     return _out(y, split)
 
 
+def layernorm_rows(x, gamma, beta=None, eps=1e-5, split=False, variant=0, cl=0, stats=False, rms=False):
+    """kern::layernorm_rows with every argument: x [..., C] (bf16, or fp32 with split), the statistics
+    over the first `cl` columns (0 = C; the rest are stored pad columns, written 0).  rms: RMSNorm,
+    y = x * rsqrt(mean(x^2) + eps) * gamma (beta unused).  stats: statistics mode, returns the fp32
+    [rows, 2] (mean, rstd) pairs ((0, rstd) with rms) instead of the rows."""
+    import torch
+
+    C = x.shape[-1]
+    rows = x.numel() // C
+    y = torch.empty(((2,) if split else ()) + tuple(x.shape), dtype=torch.bfloat16, device=x.device)
+    st = torch.empty((rows, 2), dtype=torch.float32, device=x.device) if stats else None
+    xin, gm = _in(x, split), gamma.float().contiguous()
+    bt = None if beta is None else beta.float().contiguous()
+    rc = native.kernels().die_kern_layernorm_ex(_ptr(xin), 0 if stats else _ptr(y), _ptr(gm), _ptr(bt), float(eps), rows, C,
+                                                _stream(), int(split), int(cl), int(variant), _ptr(st), int(rms))
+    _check(rc, "layernorm_rows")
+    return st if stats else _out(y, split)
+
+
+def rope_rows(xbuf, cos, sin, B, S, H, D, col=0, split=False, ybuf=None, check=True):
+    """Rotary position embedding (kern::rope_rows) on stored rows.  xbuf: bf16 [B*S, ldx] (split:
+    [2, B*S, ldx], the hi / lo planes) with head h at columns col + [h*D, (h+1)*D) -- col / ldx place
+    the block inside a wider (fused QKV) buffer; cos / sin: fp32 [S, D]; ybuf (default: a fresh dense
+    one): bf16 [(2,) B*S, ldy], head h at columns [h*D, (h+1)*D), written in place.  Returns ybuf, or
+    with check=False the pair (hipError code, ybuf) without raising."""
+    import torch
+
+    ldx = int(xbuf.shape[-1])
+    if ybuf is None:
+        ybuf = torch.empty(((2,) if split else ()) + (B * S, H * D), dtype=torch.bfloat16, device=xbuf.device)
+    ldy = int(ybuf.shape[-1])
+    assert xbuf.is_contiguous() and ybuf.is_contiguous() and cos.is_contiguous() and sin.is_contiguous()
+    assert xbuf.dtype == torch.bfloat16 and ybuf.dtype == torch.bfloat16
+    assert cos.dtype == torch.float32 and sin.dtype == torch.float32
+    rc = native.kernels().die_kern_rope_rows(_ptr(xbuf) + 2 * int(col), _ptr(ybuf), _ptr(cos), _ptr(sin), B, S, H, D, ldx,
+                                             ldy, _stream(), int(split))
+    if not check:
+        return rc, ybuf
+    _check(rc, "rope_rows")
+    return ybuf
+
+
 def tokens_assemble(patches, cls=None, pos=None, split=False):
     """patches [B, S0, C] bf16, cls [C] f32, pos [S0+1, C] f32 -> [B, S0+1, C] bf16."""
     import torch
