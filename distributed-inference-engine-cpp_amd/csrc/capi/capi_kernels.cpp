@@ -339,6 +339,16 @@ int die_kern_attention_keymask(uint64_t q, uint64_t k, uint64_t v, uint64_t out,
                                           P<const int>(kend)));
 }
 
+// die_kern_attention_keymask plus kv_heads: k / v hold kv_heads heads (0 or H: the same launch as without)
+int die_kern_attention_gqa(uint64_t q, uint64_t k, uint64_t v, uint64_t out, int B, int Sq, int H, int D, int ldq,
+                           int ldk, int ldv, int ldo, float scale, uint64_t stream, int split, uint64_t bias,
+                           int bias_heads, int Sp, int causal, uint64_t kvis, uint64_t kend, int kv_heads) {
+  return static_cast<int>(kern::attention(P<const uint16_t>(q), P<const uint16_t>(k), P<const uint16_t>(v),
+                                          P<uint16_t>(out), B, Sq, H, D, ldq, ldk, ldv, ldo, scale, S(stream), split,
+                                          P<const float>(bias), bias_heads, Sp, causal, P<const float>(kvis),
+                                          P<const int>(kend), kv_heads));
+}
+
 // bias: fp32 [bias_heads][Sq][Sp] pre-multiplied by log2(e) (kernels.h attention), 0 = none
 int die_kern_attention_masked(uint64_t q, uint64_t k, uint64_t v, uint64_t out, int B, int Sq, int H, int D, int ldq,
                               int ldk, int ldv, int ldo, float scale, uint64_t stream, int split, uint64_t bias,
@@ -532,6 +542,16 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
         e["bias_heads"] = o.bias_heads;  // 0: no table, 1: one slice shared by the heads, nh: per head
         e["causal"] = o.causal != 0;
         e["key_mask"] = o.key_mask != 0;  // the request's padding mask (key data from the embed_tokens op)
+        e["kv_heads"] = o.kv_heads;  // K / V heads stored (< nh: grouped-query attention)
+        e["heads"] = o.nh;
+        e["head_dim"] = o.hd;
+        Json cols = Json::array(), lds = Json::array();  // column offset / row pitch of Q, K, V in their buffers
+        for (int r = 0; r < 3; ++r) {
+          cols.push_back(o.col[r]);
+          lds.push_back(o.ld[r]);
+        }
+        e["cols"] = cols;
+        e["lds"] = lds;
         if (o.bias_heads) {  // the folded table, back in natural units: sum of its finite entries, count of -inf
           const int Sp = kern::key_pitch(o.S);
           const float* t = reinterpret_cast<const float*>(p.params.data() + o.bias_off);

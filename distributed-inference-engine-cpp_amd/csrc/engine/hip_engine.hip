@@ -750,6 +750,20 @@ class HipEngine : public Engine {
         else j["pad_compare"] = "none";
       }
     }
+    {  // the attention ops' shape: heads over stored K / V heads (kv_heads < heads: grouped-query attention) and masks
+      Json at = Json::array();
+      for (const PlanOp& op : plan_.ops)
+        if (op.kind == PlanOp::ATTENTION) {
+          Json o = Json::object();
+          o["heads"] = op.nh;
+          o["kv_heads"] = op.kv_heads;
+          o["head_dim"] = op.hd;
+          o["causal"] = op.causal != 0;
+          o["key_mask"] = op.key_mask != 0;
+          at.push_back(o);
+        }
+      j["attention"] = at;
+    }
     j["inputs"] = input_segments_json(plan_.inputs);  // the graph inputs as segments of a request
     j["precision"] = sp_ ? "fp32" : "bf16";
     j["gflop_per_image"] = plan_.flops_per_sample / 1e9;
@@ -1523,7 +1537,7 @@ class HipEngine : public Engine {
                               op.bias_heads ? prm(op.bias_off) : nullptr, op.bias_heads,
                               op.bias_heads || op.key_mask ? kern::key_pitch(op.S) : 0, op.causal,
                               op.key_mask ? static_cast<const float*>(buf(op.in4)) : nullptr,
-                              op.key_mask ? static_cast<const int*>(buf(op.in5)) : nullptr);
+                              op.key_mask ? static_cast<const int*>(buf(op.in5)) : nullptr, op.kv_heads);
           break;
         case PlanOp::EMBED_TOKENS:
           if (op.in_ld > 0) {  // several graph inputs: segments of the packed request rows
@@ -1664,6 +1678,7 @@ class HipEngine : public Engine {
         o["bias_heads"] = op.bias_heads;
         o["causal"] = op.causal != 0;
         o["key_mask"] = op.key_mask != 0;
+        o["kv_heads"] = op.kv_heads;
       }
       if (op.kind == PlanOp::POOL_TOKENS) {
         o["masked"] = op.key_mask != 0;

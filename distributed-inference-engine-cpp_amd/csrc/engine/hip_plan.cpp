@@ -42,6 +42,8 @@ struct Val {
     TOKCAT,      // Concat([cls, patch rows], axis=1)
     TOKEN_IDS,   // the rank-2 graph input [N, S] read as token ids (fp32 in the input buffer; H = S)
     KEYVIS,      // per-key boolean derived from the ids (padding): a pad test, a polarity, a shape
+    KVREP,       // HF repeat_kv in progress on a heads view [N, Hkv, S, hd]: stage 1 = after Unsqueeze(2)
+                 // [N, Hkv, 1, S, hd], 2 = after Expand [N, Hkv, G, S, hd] (kvg = G); the other fields = the view
     POOLV,       // masked mean pooling in progress (stage 0: rows x key mask [N, S, D], 1: their sum over the
                  // tokens [N, D], 2: the count of visible tokens [N, D] / [N, 1]); buf / C / cl / H = the rows
     UNKNOWN      // produced by a node the planner could not lower (support report)
@@ -61,6 +63,9 @@ struct Val {
   std::vector<float> asc, ash;
   // HEADS / ATTN
   int nh = 0, hd = 0;
+  // HEADS behind a repeat_kv: nh counts the LOGICAL heads, the buffer stores nh / kvg of them and
+  // logical head h is stored head h / kvg (no copy is made); 0 = no repeat
+  int kvg = 0;
   std::array<int, 4> perm{{0, 1, 2, 3}};
   int q = -1, k = -1, v = -1, stage = 0;
   float scale = 1.f;
@@ -393,6 +398,7 @@ class Planner {
     const Node& n = m_.nodes[idx];
     const std::string& op = n.op_type;
     if (token_node(n)) return lower_token_node(idx);
+    if (kv_repeat_node(n)) return lower_kv_repeat(idx);
     if (lower_shape_op(idx)) return;
     if ((op == "Mul" || op == "Slice") && rope_anchor(n)) return lower_rope(idx);
     if ((op == "Pow" || (op == "Mul" && n.inputs.size() == 2 && n.in(0) == n.in(1))) && rmsnorm_anchor(n)) return lower_rmsnorm(idx);
@@ -1007,7 +1013,10 @@ class Planner {
       if (x.kind == Val::GRAPH_IN || x.kind == Val::NHWC) s.ints = {kBatchDim, x.C, x.H, x.W};
       else if (x.kind == Val::ROWS_BF16 && x.rank == 3) s.ints = {kBatchDim, x.H * x.W, x.C};
       else if (x.kind == Val::ROWS_BF16) s.ints = {kBatchDim, x.C};
-      else s.known = false;
+      else if (x.kind == Val::HEADS) {
+        const int64_t base[4] = {kBatchDim, x.H, x.nh, x.hd};
+        for (int i = 0; i < 4; ++i) s.ints.push_back(base[x.perm[i]]);
+      } else s.known = false;
       define(n.outputs[0], s);
       return true;
     }
@@ -1040,6 +1049,108 @@ class Planner {
     }
     for (auto& o : n.outputs) define(o, s);
     return true;
+  }
+
+  // ---- grouped-query attention: HF's repeat_kv on a K / V heads view -------------------------------
+  // x [N, Hkv, S, hd] (the bhsd permutation, after the head Transpose and any rope op) ->
+  // Unsqueeze(axes [2]) -> Expand to [., Hkv, G, S, hd] -> Reshape to [., Hkv * G, S, hd]: a heads view
+  // of the SAME buffer with nh = Hkv * G and kvg = G.  No op, no copy; the attention op reads stored
+  // head h / G for logical head h (PlanOp::kv_heads).
+  bool kv_repeat_node(const Node& n) const {
+    for (size_t i = 0; i < n.inputs.size(); ++i) {
+      auto it = vid_.find(n.inputs[i]);
+      if (it == vid_.end()) continue;
+      const Val& x = vals_[it->second];
+      if (x.kind == Val::KVREP) return true;
+      if (i == 0 && x.kind == Val::HEADS && n.op_type == "Unsqueeze") return true;
+    }
+    return false;
+  }
+
+  void lower_kv_repeat(int idx) {
+    const Node& n = m_.nodes[idx];
+    const std::string where = n.op_type + " " + n.name + ": ";
+    const Val x = val(n.in(0), n);
+    const std::array<int, 4> bhsd{{0, 2, 1, 3}};
+    if (n.op_type == "Unsqueeze" && x.kind == Val::HEADS) {
+      std::vector<int64_t> ax;
+      if (x.perm == std::array<int, 4>{{0, 1, 2, 3}})
+        throw std::runtime_error(where + "a K/V repeat on the [N, S, H, hd] layout, before the head Transpose, is not "
+                                 "supported (repeat_kv is matched on [N, Hkv, S, hd], after the Transpose and any rotary "
+                                 "embedding)");
+      if (x.perm != bhsd || !node_axes(n, ax) || ax != std::vector<int64_t>{2})
+        throw std::runtime_error(where + "a heads view is unsqueezed only as the first node of repeat_kv: axes [2] on "
+                                 "[N, Hkv, S, hd]");
+      if (x.kvg) throw std::runtime_error(where + "the heads view already carries a K/V repeat");
+      if (graph_outputs_.count(n.outputs[0])) throw std::runtime_error(where + "a heads view cannot be a graph output");
+      Val o = x;
+      o.kind = Val::KVREP;
+      o.stage = 1;
+      define(n.outputs[0], o);
+      return;
+    }
+    if (x.kind != Val::KVREP)
+      throw std::runtime_error(where + "reads a K/V repeat in progress: repeat_kv is Unsqueeze -> Expand -> Reshape on the "
+                               "heads view alone");
+    const int Hkv = x.nh, S = x.H, hd = x.hd;
+    if (n.op_type == "Expand" && x.stage == 1) {
+      std::vector<int64_t> e;
+      if (n.inputs.size() < 2 || !ints_of(n.in(1), e))
+        throw std::runtime_error(where + "the shape of a K/V repeat must be static (a constant, or folded from Shape nodes)");
+      const bool ok = e.size() == 5 && (e[0] == 1 || e[0] == kBatchDim) && (e[1] == 1 || e[1] == Hkv) && e[2] >= 1 &&
+                      (e[3] == 1 || e[3] == S) && (e[4] == 1 || e[4] == hd);
+      if (!ok) {
+        std::string shp;
+        for (auto d : e) shp += (shp.empty() ? "" : ", ") + (d == kBatchDim ? std::string("N") : std::to_string(d));
+        throw std::runtime_error(where + "a K/V repeat expands axis 2 alone, [N, " + std::to_string(Hkv) + ", 1, " +
+                                 std::to_string(S) + ", " + std::to_string(hd) + "] -> [N, " + std::to_string(Hkv) + ", G, " +
+                                 std::to_string(S) + ", " + std::to_string(hd) + "]; got the shape [" + shp + "]");
+      }
+      if (graph_outputs_.count(n.outputs[0])) throw std::runtime_error(where + "a heads view cannot be a graph output");
+      Val o = x;
+      o.stage = 2;
+      o.kvg = static_cast<int>(e[2]);
+      define(n.outputs[0], o);
+      return;
+    }
+    if (n.op_type == "Reshape" && x.stage == 2) {
+      std::vector<int64_t> shp;
+      if (!ints_of(n.in(1), shp)) throw std::runtime_error(where + "target shape must be static");
+      const int G = x.kvg;
+      const bool ok = shp.size() == 4 && (shp[0] == 0 || shp[0] == -1 || shp[0] == kBatchDim) &&
+                      shp[1] == static_cast<int64_t>(Hkv) * G && shp[2] == S && shp[3] == hd;
+      if (!ok)
+        throw std::runtime_error(where + "a K/V repeat ends in a Reshape to [N, Hkv * G, S, hd] = [N, " +
+                                 std::to_string(Hkv * G) + ", " + std::to_string(S) + ", " + std::to_string(hd) +
+                                 "] (batch entry 0, -1 or N)");
+      // the repeated view exists for the attention MatMuls only (K through its Transpose)
+      auto only_matmuls = [&](const std::string& v, bool through_transpose, auto&& self) -> std::string {
+        if (graph_outputs_.count(v)) return "(graph output)";
+        for (int c : consumers(v)) {
+          const Node& r = m_.nodes[c];
+          if (r.op_type == "MatMul") continue;
+          if (r.op_type == "Transpose" && through_transpose) {
+            const std::string bad = self(r.outputs[0], false, self);
+            if (!bad.empty()) return bad;
+            continue;
+          }
+          return r.op_type + " " + r.name;
+        }
+        return std::string();
+      };
+      const std::string bad = only_matmuls(n.outputs[0], true, only_matmuls);
+      if (!bad.empty())
+        throw std::runtime_error(where + "the repeated K/V view is read by " + bad + ": only the attention MatMuls (and the "
+                                 "Transpose of K before Q K^T) may read it -- the repeat is never materialised");
+      Val o = x;
+      o.kind = Val::HEADS;
+      o.stage = 0;
+      o.nh = Hkv * G;
+      define(n.outputs[0], o);
+      return;
+    }
+    throw std::runtime_error(where + "reads a K/V repeat in progress: repeat_kv is Unsqueeze(axes [2]) -> Expand -> Reshape "
+                             "on the heads view alone");
   }
 
   // ---- token-id models: embedding lookup and the request's own key (padding) mask ------------------
@@ -1844,6 +1955,20 @@ class Planner {
       p.in4 = plan_.ops[key_op_].out2;
       p.in5 = plan_.ops[key_op_].out3;
     }
+    // grouped-query attention: K / V store nh / G heads (their views carry the group size)
+    const int kg = std::max(1, k.kvg);
+    p.kv_heads = q.nh / kg;
+    if (kg > 1) {
+      if (q.hd != 64 && q.hd != 128)
+        throw std::runtime_error("attention " + name + ": grouped-query attention (" + std::to_string(q.nh) + " heads over " +
+                                 std::to_string(p.kv_heads) + " K/V heads) needs head dim 64 or 128, not " + std::to_string(q.hd));
+      if (p.bias_heads)
+        throw std::runtime_error("attention " + name + ": grouped-query attention with a bias table on the scores is not "
+                                 "supported (unmasked, causal or the request's key mask only)");
+      if (q.col % 8 || k.col % 8 || v.col % 8 || (p.kv_heads * q.hd) % 8)
+        throw std::runtime_error("attention " + name + ": grouped-query attention needs Q / K / V column offsets and the "
+                                 "K/V width in multiples of 8");
+    }
     p.out = new_buf(static_cast<size_t>(S) * C * 2);
     const int buf = p.out;
     add_op(std::move(p));
@@ -2001,6 +2126,15 @@ class Planner {
     const Val a = val(n.in(0), n);
     const Val b = val(n.in(1), n);
     const std::array<int, 4> bhsd{{0, 2, 1, 3}}, bhds{{0, 2, 3, 1}};
+    if (a.kind == Val::HEADS && a.kvg > 1)
+      throw std::runtime_error("MatMul " + n.name + ": the first operand (Q, or the probabilities' place) carries a K/V "
+                               "repeat; only K and V of an attention are repeated per group");
+    if (a.kind == Val::HEADS && b.kind == Val::HEADS && a.perm == bhsd && b.perm == bhds && a.hd == b.hd && a.nh != b.nh)
+      throw std::runtime_error("MatMul " + n.name + ": Q has " + std::to_string(a.nh) + " heads and K " + std::to_string(b.nh) +
+                               (b.kvg ? " (" + std::to_string(b.nh / b.kvg) + " stored x groups of " + std::to_string(b.kvg) + ")"
+                                      : std::string()) +
+                               ": grouped-query attention needs K and V repeated to the query heads (repeat_kv with "
+                               "G = heads / kv_heads)");
     if (a.kind == Val::HEADS && b.kind == Val::HEADS && a.perm == bhsd && b.perm == bhds && a.nh == b.nh &&
         a.hd == b.hd) {
       Val s;
@@ -2012,6 +2146,11 @@ class Planner {
       return;
     }
     if (a.kind == Val::ATTN && a.stage == 1 && b.kind == Val::HEADS && b.perm == bhsd) {
+      const int kg = std::max(1, vals_[a.k].kvg), vg = std::max(1, b.kvg);
+      if (kg != vg || b.nh != vals_[a.k].nh)
+        throw std::runtime_error("MatMul " + n.name + ": K is repeated over groups of " + std::to_string(kg) + " heads (" +
+                                 std::to_string(vals_[a.k].nh) + " in all) and V over groups of " + std::to_string(vg) + " (" +
+                                 std::to_string(b.nh) + "): grouped-query attention needs one group size for both");
       Val c = a;
       c.stage = 2;
       c.v = vid_.at(n.in(1));

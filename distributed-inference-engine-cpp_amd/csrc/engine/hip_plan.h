@@ -167,6 +167,9 @@ struct PlanOp {
   // ATTENTION with the request's key (padding) mask: in4 / in5 = the kvis / kend buffers of the plan's
   // EMBED_TOKENS op (kern::attention); combines with a bias table, never with causal
   int key_mask = 0, in4 = -1, in5 = -1;
+  // ATTENTION: heads stored in in2 / in3 (K / V).  nh: every query head its own; a divisor of nh:
+  // grouped-query attention, query head h reads stored head h / (nh / kv_heads) (kern::attention)
+  int kv_heads = 0;
   PadTest pad;            // EMBED_TOKENS writing key data (out2 >= 0)
   int in_ld = 0, seg_ids = 0, seg_types = -1, type_rows = 0;  // EMBED_TOKENS of a model with several graph inputs
   size_t type_off = SIZE_MAX;

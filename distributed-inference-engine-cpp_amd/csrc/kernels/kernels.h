@@ -338,7 +338,8 @@ hipError_t decode_json_numbers(const unsigned char* text, const long long* offs,
 // true when the streaming attention kernel is built in (any sequence length; else S <= 256)
 // Streaming attention variant (measurement switch, process-wide): 0 = K/V staged one tile ahead
 // (default), 1 = two tiles ahead, 2 = 0 with the natural (not XCD-aware) block mapping, 3 = 0 with
-// contiguous pair ranges per XCD.
+// contiguous pair ranges per XCD, 4 = 0 with kv_heads == H launched through the GQA mode where that
+// mode takes the case (head dim 64 / 128, no bias table): groups of one, for tests against variant 0.
 void set_attention_variant(int v);
 bool attention_any_length();
 // Head dim / sequence length the attention launcher takes (streaming kernel: head dim 32, 64, 80,
@@ -395,10 +396,16 @@ hipError_t gather_rows(const uint16_t* x, uint16_t* y, int B, int S, int idx, in
 // such constant masks.
 // Wrong bias_heads / Sp / alignment, a key mask together with causal, or a mask on a build without
 // the streaming kernel: hipErrorInvalidValue, nothing launched.
+// kv_heads (grouped-query / multi-query attention): k and v hold kv_heads heads (kv_heads * D
+// columns at their pitch) and query head h reads stored head h / (H / kv_heads).  0 or H: every head
+// its own K/V, the launch above bit for bit.  Otherwise the streaming kernel's GQA mode: D = 64 or
+// 128, unmasked, causal or key-masked.  A bias table, another head dim, H % kv_heads != 0, pitches
+// below kv_heads * D or q / k / v not 16-byte aligned (a column offset that is no multiple of 8):
+// hipErrorInvalidValue, nothing launched.
 hipError_t attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, int B, int S, int H,
                      int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t s, int split = 0,
                      const float* bias = nullptr, int bias_heads = 0, int Sp = 0, int causal = 0,
-                     const float* kvis = nullptr, const int* kend = nullptr);
+                     const float* kvis = nullptr, const int* kend = nullptr, int kv_heads = 0);
 // Row pitch Sp of the bias table and of the key data kvis for sequences of S keys: S rounded up to 32.
 inline int key_pitch(int S) { return (S + 31) / 32 * 32; }
 // Embedding lookup on fp32 token ids [B][S]: out[b, s, :] = table[idx(ids[b, s])] + pos[s] + type,

@@ -679,6 +679,10 @@ struct AttnGeom {
     if (!SPLIT || !(bias || causal || keymask)) return WAVES_PER_SIMD;
     return HD == 64 ? 2 : HD == 80 || (HD == 96 && (bias || keymask)) ? 1 : WAVES_PER_SIMD;
   }
+  // GQA mode (head dim 64 / 128): the bounds of the same mode of the per-head mapping -- the item
+  // arithmetic runs once before the tile loop and holds no register across it (resource figures:
+  // profiles/gqa_attention.md)
+  static constexpr int waves_per_simd_gqa(bool causal, bool keymask) { return waves_per_simd(false, causal, keymask); }
 };
 
 //
@@ -702,13 +706,25 @@ struct AttnGeom {
 // A tile can be all -inf for a row while the row's running max is still -inf (a band mask from
 // query 32 on): the masked modes subtract 0 instead of that max, so p = alpha = 0 and o, l stay 0
 // until the row's first visible key.  A row with NO visible key is undefined (callers reject it).
-template <bool SPLIT, bool DEEP, int HD, bool BIAS = false, bool CAUSAL = false, bool KEYMASK = false>
-__global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAUSAL, KEYMASK))) void attention_stream_kernel(
+//
+// GQA mode (compile-time; grouped-query / multi-query attention): k and v hold Hkv = H / grp heads
+// (Hkv * HD columns at their own pitch) and query head h reads stored head h / grp.  A block belongs
+// to one (image, kv head) pair -- blockIdx.y / gridDim.y count KV heads -- and stages that head's
+// K/V tiles once for four consecutive ITEMS of the pair, one per wave: item t = 4 qblk + wave is
+// (query tile t / grp of 32 queries, head kvh * grp + t % grp), the head innermost so a block's waves
+// sit on neighbouring query ranges; a wave with t >= ceil(S / 32) * grp is idle.  What was
+// block-uniform and becomes wave-uniform: the Q fragment loads and the output row pointer.  The
+// tile math, the key mask (per sample) and the XCD map (pairs = Hkv * B) are the per-head mapping's;
+// CAUSAL walks the tiles up to the last active item's last query.  No BIAS table in this mode.
+template <bool SPLIT, bool DEEP, int HD, bool BIAS = false, bool CAUSAL = false, bool KEYMASK = false, bool GQA = false>
+__global__ __launch_bounds__(256, (GQA ? AttnGeom<HD, SPLIT>::waves_per_simd_gqa(CAUSAL, KEYMASK)
+                                       : AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAUSAL, KEYMASK))) void attention_stream_kernel(
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ v,
     uint16_t* __restrict__ out, int S, int ldq, int ldk, int ldv, int ldo, float scale_log2, int xcd_map,
     const float* __restrict__ bias, long long bias_hs, int Sp, const float* __restrict__ kvis,
-    const int* __restrict__ kend) {
+    const int* __restrict__ kend, int grp) {
   static_assert(!(KEYMASK && CAUSAL), "a key mask never combines with the causal flag");
+  static_assert(!(GQA && (BIAS || DEEP)), "the GQA mode has no bias table and stages one tile ahead");
   using G = AttnGeom<HD, SPLIT>;
   constexpr int NP = SPLIT ? 2 : 1;
   constexpr int KT = 32;  // keys per tile
@@ -744,6 +760,11 @@ __global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAU
   const long long rows = static_cast<long long>(gridDim.z) * S;  // plane distances: rows x pitch
   // CAUSAL: the block's last query sees keys below min(S, 128 qblk + 128) only (block-uniform)
   int klim = CAUSAL && qblk * 128 + 128 < S ? qblk * 128 + 128 : S;
+  if constexpr (GQA && CAUSAL) {  // the last item's query tile, clamped to the last tile of the sequence
+    const int nqt = (S + KT - 1) / KT, lt = (4 * qblk + 3) / grp;
+    klim = KT * (lt < nqt - 1 ? lt : nqt - 1) + KT;
+    klim = klim < S ? klim : S;
+  }
   // KEYMASK: keys from kend[b] on are padding (block-uniform; clamped: the value is device data)
   if constexpr (KEYMASK) {
     const int ke = kend[b];
@@ -781,7 +802,15 @@ __global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAU
       }
     }
   };
-  const int q0 = qblk * 128 + wave * 32;
+  // GQA: the wave's item -> (query tile, head of the group); hq = the query / output head (h: the
+  // K/V head the block stages).  An item past the last one has q0 >= S, like an idle wave.
+  int q0 = qblk * 128 + wave * 32, hq = h;
+  if constexpr (GQA) {
+    const int t = __builtin_amdgcn_readfirstlane(4 * qblk + wave);
+    const int qtile = t / grp;
+    hq = h * grp + (t - qtile * grp);
+    q0 = KT * qtile;
+  }
   const bool active = q0 < S;  // wave-uniform; an idle wave still loads tiles and meets every barrier
   const int r = lane & 31, hh = lane >> 5;
   bf16x8 qf[NP][NKS];
@@ -793,7 +822,7 @@ __global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAU
       for (int ks = 0; ks < NKS; ++ks) {
         uint4 t = make_uint4(0, 0, 0, 0);
         if (qr < S)
-          t = *reinterpret_cast<const uint4*>(q + pl * rows * ldq + (rowbase + qr) * ldq + h * HD + ks * 16 + hh * 8);
+          t = *reinterpret_cast<const uint4*>(q + pl * rows * ldq + (rowbase + qr) * ldq + hq * HD + ks * 16 + hh * 8);
         qf[pl][ks] = __builtin_bit_cast(bf16x8, t);
       }
   }
@@ -949,7 +978,7 @@ __global__ __launch_bounds__(256, (AttnGeom<HD, SPLIT>::waves_per_simd(BIAS, CAU
   if (qr >= S) return;
   // KEYMASK: a row without a visible key (an all-pad sample: no tile walked, o = l = 0) is written 0
   const float inv = KEYMASK && l == 0.f ? 0.f : 1.f / l;
-  uint16_t* orow = out + (rowbase + qr) * ldo + h * HD;
+  uint16_t* orow = out + (rowbase + qr) * ldo + hq * HD;
   const long long oplane = rows * ldo;
 #pragma unroll
   for (int g4 = 0; g4 < 4; ++g4) {
@@ -1214,14 +1243,25 @@ bool attention_supported(int D, int S, bool masked) {
 
 namespace {
 int g_attn_variant = 0;  // 0: K/V staged one tile ahead, 1: two tiles ahead (DEEP), 2: 0 without the XCD map
+                         // 3: contiguous pair ranges per XCD, 4: 0 with kv_heads == H through the GQA mapping
 }
 void set_attention_variant(int v) { g_attn_variant = v; }
 
 hipError_t attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, int B, int S, int H,
                      int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t s, int split,
-                     const float* bias, int bias_heads, int Sp, int causal, const float* kvis, const int* kend) {
+                     const float* bias, int bias_heads, int Sp, int causal, const float* kvis, const int* kend,
+                     int kv_heads) {
   const bool masked = bias != nullptr || causal != 0 || kvis != nullptr;
   if (!attention_supported(D, S, masked) || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4) return hipErrorInvalidValue;
+  if (kv_heads < 0 || kv_heads > H) return hipErrorInvalidValue;
+  if (kv_heads == 0) kv_heads = H;
+  // grouped-query attention: the streaming kernel's GQA mode, head dim 64 / 128, no bias table
+  // (variant 4 sends kv_heads == H through it too, where it takes the case: groups of one)
+  const bool gqa_ok = kAttnStream && (D == 64 || D == 128) && !bias;
+  const bool gqa = kv_heads != H || (g_attn_variant == 4 && gqa_ok);
+  if (gqa && (!gqa_ok || H % kv_heads || reinterpret_cast<uintptr_t>(q) % 16 || reinterpret_cast<uintptr_t>(k) % 16 ||
+              reinterpret_cast<uintptr_t>(v) % 16 || ldk < kv_heads * D || ldv < kv_heads * D))
+    return hipErrorInvalidValue;
   if (bias) {  // [1 or H][S][Sp] fp32, rows of Sp = S rounded up to 32 (16-byte loads, in bounds in the last tile)
     if ((bias_heads != 1 && bias_heads != H) || Sp != (S + 31) / 32 * 32 || reinterpret_cast<uintptr_t>(bias) % 16)
       return hipErrorInvalidValue;
@@ -1239,11 +1279,32 @@ hipError_t attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, ui
     const bool deep = g_attn_variant == 1;
     // variant 2: the natural block mapping, 3: contiguous pair ranges per XCD (measurement)
     const int xcd_map = g_attn_variant == 2 ? 0 : g_attn_variant == 3 ? 2 : 1;
+    if (gqa) {  // blocks of four (query tile, head of the group) items per (image, kv head) pair
+      const int grp = H / kv_heads, items = (S + 31) / 32 * grp;
+      const dim3 ggrid((items + 3) / 4, kv_heads, B);
+#define ATTN_GQA(SP, HDV, CA, KM)                                                                                      \
+  hipLaunchKernelGGL((attention_stream_kernel<SP, false, HDV, false, CA, KM, true>), ggrid, dim3(256), 0, s, q, k, v, out, \
+                     S, ldq, ldk, ldv, ldo, sl2, xcd_map, static_cast<const float*>(nullptr), 0LL, Sp, kvis, kend, grp)
+#define ATTN_GQA_HD(HDV)                                       \
+  if (split) {                                                 \
+    if (kvis) ATTN_GQA(true, HDV, false, true);                \
+    else if (causal) ATTN_GQA(true, HDV, true, false);         \
+    else ATTN_GQA(true, HDV, false, false);                    \
+  } else {                                                     \
+    if (kvis) ATTN_GQA(false, HDV, false, true);               \
+    else if (causal) ATTN_GQA(false, HDV, true, false);        \
+    else ATTN_GQA(false, HDV, false, false);                   \
+  }
+      if (D == 64) { ATTN_GQA_HD(64) } else { ATTN_GQA_HD(128) }
+#undef ATTN_GQA_HD
+#undef ATTN_GQA
+      return hipGetLastError();
+    }
     if (masked) {  // one-tile-ahead staging only (the DEEP measurement variant stays unmasked)
       const long long bias_hs = bias && bias_heads == H && H > 1 ? static_cast<long long>(S) * Sp : 0;
 #define ATTN_MASKED(SP, HDV, BI, CA, KM)                                                                             \
   hipLaunchKernelGGL((attention_stream_kernel<SP, false, HDV, BI, CA, KM>), grid, dim3(256), 0, s, q, k, v, out, S, ldq, \
-                     ldk, ldv, ldo, sl2, xcd_map, bias, bias_hs, Sp, kvis, kend)
+                     ldk, ldv, ldo, sl2, xcd_map, bias, bias_hs, Sp, kvis, kend, 0)
 #define ATTN_MASKED_HD(HDV)                                            \
   if (split) {                                                         \
     if (kvis && bias) ATTN_MASKED(true, HDV, true, false, true);       \
@@ -1272,7 +1333,7 @@ hipError_t attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, ui
 #define ATTN_LAUNCH(SP, DP, HDV)                                                                                   \
   hipLaunchKernelGGL((attention_stream_kernel<SP, DP, HDV>), grid, dim3(256), 0, s, q, k, v, out, S, ldq, ldk, ldv, ldo, \
                      sl2, xcd_map, static_cast<const float*>(nullptr), 0LL, 0, static_cast<const float*>(nullptr),    \
-                     static_cast<const int*>(nullptr))
+                     static_cast<const int*>(nullptr), 0)
 #define ATTN_HD(HDV)                          \
   if (split && deep) ATTN_LAUNCH(true, true, HDV);    \
   else if (split) ATTN_LAUNCH(true, false, HDV);      \

@@ -74,6 +74,10 @@ mix a ResNet / ViT never exercises, random weights, written by the in-tree ONNX 
               masked-mean + LpNormalization tail.  Output [N, 128], unit length.
 * `llama_enc_rmsnode` the same body and weights with every RMSNorm written as one RMSNormalization node
               (opset 23).
+* `gqa_enc` / `mqa_causal` / `gqa_hd128`  grouped-query attention (K / V projected to fewer heads than Q
+              and repeated per group by HF's repeat_kv: Unsqueeze -> Expand -> Reshape) on the `llama_enc`,
+              `gpt_causal` and `rope_bert` bodies; see `build_gqa_model`.  expand_kv=True builds the
+              multi-head twin from the same weights.
 `synthetic_input(model, batch)` gives inputs of the right shape (token-id models: float32 ids in
 [1, V), sample i padded with 0 past a length that cycles through 1, 32, S, 45, 33, every third sample
 with one interior pad id).  The CPU executor is the fp32
@@ -120,13 +124,18 @@ SPECS = {
     "rope_bert_nshd": dict(seq=24, dim=256, heads=2, ffn=512, layers=2, classes=3, theta=10000.0, layout="nshd"),
     "llama_enc": dict(seq=160, dim=128, heads=4, ffn=256, layers=2, vocab=1000, pad=0, theta=10000.0, eps=1e-6),
     "llama_enc_rmsnode": dict(seq=160, dim=128, heads=4, ffn=256, layers=2, vocab=1000, pad=0, theta=10000.0, eps=1e-6),
+    "gqa_enc": dict(seq=160, dim=256, heads=4, kv_heads=2, ffn=512, layers=2, vocab=1000, pad=0, theta=10000.0, eps=1e-6,
+                    body="llama"),
+    "mqa_causal": dict(seq=72, dim=256, heads=4, kv_heads=1, ffn=512, layers=2, classes=3, body="gpt"),
+    "gqa_hd128": dict(seq=40, dim=768, heads=6, kv_heads=2, ffn=512, layers=1, classes=3, theta=10000.0, body="rope_bert"),
 }
 
 MASKED = ("gpt_causal", "bert_relpos", "bert_window", "bert_keymask")
 MULTI_INPUT = ("bert_hf3", "sbert_hf2", "bert_hf3_maskfirst")  # input_ids + attention_mask [+ token_type_ids]
 ROPE_BERT = ("rope_bert", "rope_bert_nshd")
 LLAMA = ("llama_enc", "llama_enc_rmsnode")
-TOKEN_IDS = ("bert_ids", "bert_ids_hf", "sbert_ids", "sbert_ids_hf", "sbert_cls") + MULTI_INPUT + LLAMA
+GQA = ("gqa_enc", "mqa_causal", "gqa_hd128")  # K / V with fewer heads than Q (build_gqa_model)
+TOKEN_IDS = ("bert_ids", "bert_ids_hf", "sbert_ids", "sbert_ids_hf", "sbert_cls") + MULTI_INPUT + LLAMA + ("gqa_enc",)
 INPUT_NAMES = {"ids": "input_ids", "mask": "attention_mask", "types": "token_type_ids"}
 
 
@@ -896,6 +905,151 @@ def build_ln_offset(seed: int = 0, opset: int = 17, offset: float = 60.0) -> Tup
     return g.model_proto(opset=opset), {}
 
 
+def repeat_kv_nodes(g, x, Hkv, G, S, hd, p, full_shape=True, batch=0):
+    """HF's repeat_kv export on the heads view x [N, Hkv, S, hd]: Unsqueeze(2) -> Expand -> Reshape to
+    [N, Hkv * G, S, hd].  full_shape: the Expand target is [1, Hkv, G, S, hd], else [1, 1, G, 1, 1];
+    batch: the Reshape's batch entry (0 or -1)."""
+    u = g.node("Unsqueeze", [x, g.const(np.array([2], np.int64), "repeat_axis")], name=p + "repeat/unsqueeze")
+    shape = [1, Hkv, G, S, hd] if full_shape else [1, 1, G, 1, 1]
+    e = g.node("Expand", [u, g.const(np.array(shape, np.int64), "repeat_shape")], name=p + "repeat/expand")
+    return g.node("Reshape", [e, g.const(np.array([batch, Hkv * G, S, hd], np.int64), "repeat_merge")],
+                  name=p + "repeat/merge")
+
+
+def build_gqa_model(seed: int = 0, opset: int = 17, spec: str = "gqa_enc",
+                    expand_kv: bool = False) -> Tuple[bytes, Dict[str, np.ndarray]]:
+    """The grouped-query attention models: K and V are projected to kv_heads < heads heads and every
+    K/V head is repeated over its group of heads / kv_heads query heads by HF's repeat_kv
+    (`repeat_kv_nodes`, after the head Transpose and after RoPE on K).
+    * `gqa_enc`     the `llama_enc` body (token ids, RMSNorm, RoPE, bias-free projections, SwiGLU, ids-derived
+                    key mask, masked mean + L2 normalisation): 4 heads of 64 over 2 K/V heads, 160 tokens.
+    * `mqa_causal`  the `gpt_causal` body (float embeddings, pre-LN, projections with biases, the causal
+                    Where, a classifier head): 4 heads of 64 over ONE K/V head, 72 tokens.
+    * `gqa_hd128`   the `rope_bert` body (float embeddings, post-LN, RoPE, a classifier head): 6 heads of 128
+                    over 2 K/V heads (groups of 3), 40 tokens.
+    expand_kv: the multi-head twin -- the same weights with the K / V projection columns (and biases)
+    repeated per group and no repeat nodes; it computes what the GQA model computes.
+    Returns (model bytes, initializers)."""
+    from ..utils.onnx_writer import INT64
+
+    s = SPECS[spec]
+    rng = _rng(seed)
+    S, D, H, Hkv, F = s["seq"], s["dim"], s["heads"], s["kv_heads"], s["ffn"]
+    hd, G = D // H, H // Hkv
+    Dkv = Hkv * hd
+    body = s["body"]  # "llama", "gpt" or "rope_bert"
+    g = GraphBuilder(name=spec + ("_expanded" if expand_kv else ""))
+    one = g.const(np.array(1.0, np.float32), "one")
+    if body == "llama":
+        x = g.input("input_ids", ["N", S])
+        ids = g.node("Cast", [x], name="ids_int", to=INT64)
+        table = g.init("embed_tokens.weight", (0.5 * rng.standard_normal((s["vocab"], D))).astype(np.float32))
+        h = g.node("Gather", [table, ids], name="embed_tokens", axis=0)
+        mask_f = g.node("Cast", [g.node("Greater", [x, g.const(np.array(0, np.float32), "pad_id")], name="attention_mask")],
+                        name="attention_mask_f", to=1)
+        m = g.node("Unsqueeze", [mask_f, g.const(np.array([1, 2], np.int64), "mask_axes")], name="extended_mask")
+        key_term = g.node("Mul", [g.node("Sub", [one, m], name="inverted_mask"),
+                                  g.const(np.array(-10000.0, np.float32), "mask_value")], name="additive_mask")
+    else:
+        x = g.input("embeddings", ["N", S * D])
+        h = g.node("Reshape", [x, g.const(np.array([0, S, D], np.int64), "seq_shape")], name="to_tokens")
+    q_shape = g.const(np.array([0, 0, H, hd], np.int64), "heads_shape")
+    kv_shape = q_shape if expand_kv else g.const(np.array([0, 0, Hkv, hd], np.int64), "kv_heads_shape")
+    merge_shape = g.const(np.array([0, 0, D], np.int64), "merge_shape")
+    sqrt_d = g.const(np.array(math.sqrt(hd), np.float32), "sqrt_d")
+    sqrt2 = g.const(np.array(1.4142135381698608, np.float32), "sqrt2")
+    half = g.const(np.array(0.5, np.float32), "half")
+    two = g.const(np.array(2.0, np.float32), "two")
+    rope = body != "gpt"
+    if rope:
+        c, sn = rope_tables(S, hd, s["theta"])
+        cos, sin = g.init("rope.cos", c.reshape(1, 1, S, hd)), g.init("rope.sin", sn.reshape(1, 1, S, hd))
+    with_bias = body != "llama"
+
+    def widen(a):  # [.., Hkv * hd] -> [.., H * hd]: every K/V head's columns repeated over its group
+        return np.repeat(a.reshape(a.shape[:-1] + (Hkv, hd)), G, axis=-2).reshape(a.shape[:-1] + (D,))
+
+    def linear(inp, name, fin, fout, kv=False):
+        w = _lin(rng, fin, (fin, fout))
+        b = (0.02 * rng.standard_normal(fout)).astype(np.float32) if with_bias else None
+        if kv and expand_kv:
+            w, b = widen(w), (widen(b) if b is not None else None)
+        y = g.node("MatMul", [inp, g.init(name + ".weight", w)], name=name + ("/MatMul" if with_bias else ""))
+        return g.node("Add", [y, g.init(name + ".bias", b)], name=name + "/Add") if with_bias else y
+
+    def norm(inp, name):
+        gw = g.init(name + ".weight", (1.0 + 0.1 * rng.standard_normal(D)).astype(np.float32))
+        if body == "llama":  # torch's decomposed RMSNorm
+            var = g.node("ReduceMean", [g.node("Pow", [inp, two], name=name + "/pow")], name=name + "/mean", axes=[-1],
+                         keepdims=1)
+            inv = g.node("Div", [one, g.node("Sqrt", [g.node("Add", [var, g.const(np.array(s["eps"], np.float32), "rms_eps")],
+                                                             name=name + "/add_eps")], name=name + "/sqrt")],
+                         name=name + "/rsqrt")
+            return g.node("Mul", [gw, g.node("Mul", [inp, inv], name=name + "/normalize")], name=name + "/scale")
+        gb = g.init(name + ".bias", (0.1 * rng.standard_normal(D)).astype(np.float32))
+        return g.node("LayerNormalization", [inp, gw, gb], name=name, axis=-1, epsilon=1e-5)
+
+    def attention(a, p, layer):
+        bhsd = [0, 2, 1, 3]
+        q = g.node("Transpose", [g.node("Reshape", [linear(a, p + "q_proj", D, D), q_shape], name=p + "q_heads")],
+                   name=p + "q_perm", perm=bhsd)
+        k = g.node("Transpose", [g.node("Reshape", [linear(a, p + "k_proj", D, Dkv, kv=True), kv_shape], name=p + "k_heads")],
+                   name=p + "k_perm", perm=bhsd)
+        v = g.node("Transpose", [g.node("Reshape", [linear(a, p + "v_proj", D, Dkv, kv=True), kv_shape], name=p + "v_heads")],
+                   name=p + "v_perm", perm=bhsd)
+        if rope:
+            q = rope_nodes(g, q, cos, sin, hd, p + "q_", open_end=True)
+            k = rope_nodes(g, k, cos, sin, hd, p + "k_", open_end=True)
+        if not expand_kv:  # the two Expand shape forms and both Reshape batch entries, by layer
+            k = repeat_kv_nodes(g, k, Hkv, G, S, hd, p + "k_", full_shape=layer % 2 == 0, batch=0)
+            v = repeat_kv_nodes(g, v, Hkv, G, S, hd, p + "v_", full_shape=layer % 2 == 0, batch=-1 if layer % 2 else 0)
+        k = g.node("Transpose", [k], name=p + "k_t", perm=[0, 1, 3, 2])
+        sc = g.node("Div", [g.node("MatMul", [q, k], name=p + "scores"), sqrt_d], name=p + "scale")
+        if body == "llama":
+            sc = g.node("Add", [sc, key_term], name=p + "mask/Add")
+        elif body == "gpt":
+            tril = g.init(p + "causal_mask", np.tril(np.ones((1, 1, S, S), np.bool_)))
+            sc = g.node("Where", [tril, sc, g.const(np.array(-1e4, np.float32), "mask_fill")], name=p + "causal")
+        sc = g.node("Softmax", [sc], name=p + "softmax", axis=-1)
+        ctx = g.node("MatMul", [sc, v], name=p + "context")
+        ctx = g.node("Reshape", [g.node("Transpose", [ctx], name=p + "ctx_perm", perm=bhsd), merge_shape],
+                     name=p + "ctx_merge")
+        return linear(ctx, p + "o_proj", D, D)
+
+    def ffn(a, p):
+        if body == "llama":
+            gate, up = linear(a, p + "gate_proj", D, F), linear(a, p + "up_proj", D, F)
+            act = g.node("Mul", [g.node("Mul", [gate, g.node("Sigmoid", [gate], name=p + "silu/sigmoid")], name=p + "silu"),
+                                 up], name=p + "swiglu")
+            return linear(act, p + "down_proj", F, D)
+        m1 = linear(a, p + "intermediate", D, F)
+        t = g.node("Div", [m1, sqrt2], name=p + "gelu/div")
+        t = g.node("Add", [g.node("Erf", [t], name=p + "gelu/erf"), one], name=p + "gelu/add")
+        t = g.node("Mul", [g.node("Mul", [m1, t], name=p + "gelu/mul"), half], name=p + "gelu/half")
+        return linear(t, p + "output", F, D)
+
+    for i in range(s["layers"]):
+        p = "layer%d." % i
+        if body == "rope_bert":  # post-LN
+            h = norm(g.node("Add", [attention(h, p, i), h], name=p + "residual1"), p + "ln1")
+            h = norm(g.node("Add", [ffn(h, p), h], name=p + "residual2"), p + "ln2")
+        else:  # pre-norm: x + attn(norm(x)), x + ffn(norm(x))
+            h = g.node("Add", [h, attention(norm(h, p + "norm1"), p, i)], name=p + "residual1")
+            h = g.node("Add", [h, ffn(norm(h, p + "norm2"), p)], name=p + "residual2")
+    if body != "rope_bert":
+        h = norm(h, "norm_f")
+    if body == "llama":
+        y = _sentence_head(g, "sbert_ids_hf", h, None, mask_f)
+        g.output(y, ["N", D])
+        return g.model_proto(opset=opset), dict(g.initializers)
+    pooled = g.node("ReduceMean", [h], name="mean_pool", axes=[1], keepdims=0)
+    w = g.init("classifier.weight", _lin(rng, D, (s["classes"], D)))
+    b = g.init("classifier.bias", (0.1 * rng.standard_normal(s["classes"])).astype(np.float32))
+    y = g.node("Gemm", [pooled, w, b], name="classifier", transB=1)
+    g.output(y, ["N", s["classes"]])
+    return g.model_proto(opset=opset), dict(g.initializers)
+
+
 BUILDERS = {"mlp": build_mlp, "bert": build_bert, "se_cnn": build_se_cnn, "ratio_mlp": build_ratio_mlp,
             "ops_zoo": build_ops_zoo, "upsample_net": build_upsample_net, "token_mixer": build_token_mixer,
             "ln_wide": build_ln_wide, "ln_offset": build_ln_offset,
@@ -917,7 +1071,10 @@ BUILDERS = {"mlp": build_mlp, "bert": build_bert, "se_cnn": build_se_cnn, "ratio
             "rope_bert": lambda seed=0: build_rope_encoder(seed, spec="rope_bert"),
             "rope_bert_nshd": lambda seed=0: build_rope_encoder(seed, spec="rope_bert_nshd"),
             "llama_enc": lambda seed=0: build_llama_encoder(seed, spec="llama_enc"),
-            "llama_enc_rmsnode": lambda seed=0: build_llama_encoder(seed, spec="llama_enc_rmsnode")}
+            "llama_enc_rmsnode": lambda seed=0: build_llama_encoder(seed, spec="llama_enc_rmsnode"),
+            "gqa_enc": lambda seed=0, expand_kv=False: build_gqa_model(seed, spec="gqa_enc", expand_kv=expand_kv),
+            "mqa_causal": lambda seed=0, expand_kv=False: build_gqa_model(seed, spec="mqa_causal", expand_kv=expand_kv),
+            "gqa_hd128": lambda seed=0, expand_kv=False: build_gqa_model(seed, spec="gqa_hd128", expand_kv=expand_kv)}
 
 
 def build_onnx(name: str, seed: int = 0) -> bytes:
@@ -928,7 +1085,8 @@ def input_shape(name: str):
     s = SPECS[name]
     if name in ("mlp", "ratio_mlp"):
         return (s["in_features"],)
-    if name in ("bert", "bert_long", "bert_hd32", "bert_hd128", "token_mixer", "ln_wide", "ln_offset") + MASKED + ROPE_BERT:
+    if name in ("bert", "bert_long", "bert_hd32", "bert_hd128", "token_mixer", "ln_wide", "ln_offset") + MASKED + ROPE_BERT + \
+            ("mqa_causal", "gqa_hd128"):
         return (s["seq"] * s["dim"],)
     if name in MULTI_INPUT:  # a request row: every input's [S] in declaration order
         return (len(s["inputs"]) * s["seq"],)

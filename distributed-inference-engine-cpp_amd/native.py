@@ -774,6 +774,8 @@ def _sig_kernels():
     L.die_kern_attention_masked.argtypes = [u64] * 4 + [i] * 8 + [C.c_float, u64, i, u64, i, i, i]
     L.die_kern_attention_keymask.restype = i
     L.die_kern_attention_keymask.argtypes = [u64] * 4 + [i] * 8 + [C.c_float, u64, i, u64, i, i, i, u64, u64]
+    L.die_kern_attention_gqa.restype = i
+    L.die_kern_attention_gqa.argtypes = [u64] * 4 + [i] * 8 + [C.c_float, u64, i, u64, i, i, i, u64, u64, i]
     L.die_kern_embed_tokens.restype = i
     L.die_kern_embed_tokens.argtypes = [u64, u64, i, u64, u64, u64, i, i, i, i, u64, i, u64, u64, i, i, C.c_float, i, i]
     L.die_kern_embed_inputs.restype = i

@@ -633,8 +633,22 @@ def _attention_bias(bias, S, heads):
     return table, int(bias.shape[0]), Sp
 
 
-def _attention_launch(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, split, bias, causal, what, key_mask=None):
-    if key_mask is not None:
+def _attention_launch(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, split, bias, causal, what, key_mask=None,
+                      kv_heads=None):
+    if kv_heads is not None:  # the entry point with kv_heads (grouped-query attention), whatever the masks
+        kvis = kend = None
+        Sp = (S + 31) // 32 * 32
+        if key_mask is not None:
+            if not isinstance(key_mask, (tuple, list)) and tuple(key_mask.shape) != (B, S):
+                raise ValueError("key mask must be bool [B, S] = [%d, %d], got %s" % (B, S, tuple(key_mask.shape)))
+            kvis, kend = key_mask if isinstance(key_mask, (tuple, list)) else key_mask_data(key_mask)
+            if tuple(kvis.shape) != (B, Sp) or tuple(kend.shape) != (B,):
+                raise ValueError("key mask must be bool [B, S] or (kvis [B, Sp] fp32, kend [B] int32), B = %d, S = %d" % (B, S))
+        table, hb, _ = _attention_bias(bias, S, heads) if bias is not None else (None, 0, 0)
+        rc = native.kernels().die_kern_attention_gqa(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, _stream(), split,
+                                                     _ptr(table), hb, Sp if (table is not None or kvis is not None) else 0,
+                                                     int(bool(causal)), _ptr(kvis), _ptr(kend), int(kv_heads))
+    elif key_mask is not None:
         if not isinstance(key_mask, (tuple, list)) and tuple(key_mask.shape) != (B, S):
             raise ValueError("key mask must be bool [B, S] = [%d, %d], got %s" % (B, S, tuple(key_mask.shape)))
         kvis, kend = key_mask if isinstance(key_mask, (tuple, list)) else key_mask_data(key_mask)
@@ -654,7 +668,7 @@ def _attention_launch(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, spli
     _check(rc, what)
 
 
-def attention(q, k, v, heads, scale=None, bias=None, causal=False, key_mask=None):
+def attention(q, k, v, heads, scale=None, bias=None, causal=False, key_mask=None, kv_heads=None):
     """q/k/v: [B, S, H*D] bf16 (may be column slices of a wider tensor, row stride = stride(1)).
     Returns softmax(scale * Q K^T + bias) V merged back to [B, S, H*D] bf16.
     bias: fp32 [S, S] (shared by the heads) or [H, S, S], natural units, -inf = masked, the same for
@@ -662,7 +676,10 @@ def attention(q, k, v, heads, scale=None, bias=None, causal=False, key_mask=None
     A query row with no visible key at all is undefined (NaN in ONNX): the caller must not pass one.
     key_mask: per-sample padding, bool [B, S] with True = visible key, or the (kvis, kend) pair of
     embed_tokens() / key_mask_data(); combines with a bias, not with causal (an error).  A sample
-    without any visible key gets all-zero rows."""
+    without any visible key gets all-zero rows.
+    kv_heads: grouped-query / multi-query attention -- k / v are [B, S, kv_heads * D] and query head h
+    reads their head h // (heads // kv_heads).  Head dim 64 or 128, no bias; kv_heads = heads is the
+    multi-head launch."""
     import torch
 
     B, S, C = q.shape
@@ -672,23 +689,34 @@ def attention(q, k, v, heads, scale=None, bias=None, causal=False, key_mask=None
     out = torch.empty((B, S, C), dtype=torch.bfloat16, device=q.device)
     sc = float(scale if scale is not None else 1.0 / np.sqrt(D))
     _attention_launch(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, S, heads, D, q.stride(1), k.stride(1), v.stride(1), C,
-                      sc, 0, bias, causal, "attention", key_mask)
+                      sc, 0, bias, causal, "attention", key_mask, kv_heads)
     return out
 
 
 def set_attention_variant(v):
     """Process-wide streaming-attention variant (kernels.h set_attention_variant): 0 = K/V staged one
-    tile ahead (default), 1 = two tiles ahead."""
+    tile ahead (default), 1 = two tiles ahead, 4 = kv_heads == heads launched through the GQA mode (tests)."""
     native.kernels().die_kern_set_attention_variant(int(v))
 
 
-def attention_qkv_split(qkv, heads, scale=None, bias=None, causal=False, key_mask=None):
+def attention_qkv_split(qkv, heads, scale=None, bias=None, causal=False, key_mask=None, kv_heads=None):
     """fp32 mode: qkv [B, S, 3*C] float (Q | K | V columns) -> fp32 [B, S, C] through the split kernel
     (planes of the packed QKV rows, like the engine's fused QKV GEMM output).  bias / causal: as
-    attention() takes them (the bias is fp32 in both precisions); key_mask: likewise."""
+    attention() takes them (the bias is fp32 in both precisions); key_mask: likewise.
+    kv_heads: qkv is [B, S, (heads + 2 * kv_heads) * D] (Q | K | V with kv_heads heads each in K and V)."""
     import torch
 
     B, S, C3 = qkv.shape
+    if kv_heads is not None:
+        D = C3 // (heads + 2 * int(kv_heads))
+        C, Ckv = heads * D, int(kv_heads) * D
+        planes = split_planes(qkv)
+        out = torch.empty((2, B, S, C), dtype=torch.bfloat16, device=qkv.device)
+        sc = float(scale if scale is not None else 1.0 / np.sqrt(D))
+        base = _ptr(planes)
+        _attention_launch(base, base + 2 * C, base + 2 * (C + Ckv), _ptr(out), B, S, heads, D, C3, C3, C3, C, sc, 1, bias,
+                          causal, "attention (split)", key_mask, kv_heads)
+        return join_planes(out)
     C = C3 // 3
     D = C // heads
     planes = split_planes(qkv)  # [2, B, S, 3C]
