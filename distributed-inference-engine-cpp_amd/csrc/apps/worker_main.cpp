@@ -62,6 +62,7 @@ die::EngineOptions engine_options_from_flags(const die::Flags& f, const std::str
   eo.fuse_stem_pool = !f.b("no-fuse-stem-pool");
   eo.fuse_gap_fc = f.b("fuse-gap-fc");
   eo.fold_layernorm = !f.b("no-fold-layernorm");
+  eo.tiled_dwconv = !f.b("no-tiled-dwconv");
   eo.ln_stats_epilogue = !f.b("no-ln-stats-epilogue");
   eo.tune_in_graph = f.b("tune-in-graph");
   eo.tune_orders = !f.b("no-tune-orders");
@@ -110,7 +111,7 @@ int follower_main(die::Flags& f, sigset_t& sigs) {
 
 const std::vector<std::string> kBoolFlags = {"verbose", "deadline", "no-graphs", "no-device-decode", "dp-follower",
                                              "no-shm", "reuse-port", "dp-no-ingest", "no-pace", "no-pack-text",
-                                             "branch-streams", "coarse-buckets", "no-fuse-pairs", "no-fuse-stem-pool", "fuse-gap-fc", "no-fold-layernorm", "no-ln-stats-epilogue", "tune-in-graph", "no-tune-orders", "tune-tail", "tune-warm",
+                                             "branch-streams", "coarse-buckets", "no-fuse-pairs", "no-fuse-stem-pool", "fuse-gap-fc", "no-fold-layernorm", "no-tiled-dwconv", "no-ln-stats-epilogue", "tune-in-graph", "no-tune-orders", "tune-tail", "tune-warm",
                                              "no-efficient-batch", "no-batch-balance",
                                              "dp-force-merge"};
 
@@ -137,7 +138,7 @@ int main(int argc, char** argv) {
               << "  --device auto|hip|cpu (auto)  --device-id N (0)  --precision fp32|bf16 (fp32)\n"
               << "  --pipeline-depth N (3)  --no-graphs  --no-device-decode  --stage-slots N (0 = off, -1 = auto)  --exec-streams N (1)\n"
               << "  --no-pace  --no-pack-text  --branch-streams  --copy-streams N (0 = auto)  --bucket-div N (8)  --coarse-buckets\n"
-              << "  --pace-lead-scale X (1)  --splitk-fused-margin X (0)  --completion-poll-us N (0)  --no-fuse-pairs  --no-fuse-stem-pool  --fuse-gap-fc  --no-fold-layernorm  --no-ln-stats-epilogue  --tune-in-graph  --no-tune-orders  --tune-tail  --tune-warm  --no-efficient-batch  --efficient-batch-tol X (0)  --tune-cache PATH|auto|''\n"
+              << "  --pace-lead-scale X (1)  --splitk-fused-margin X (0)  --completion-poll-us N (0)  --no-fuse-pairs  --no-fuse-stem-pool  --fuse-gap-fc  --no-fold-layernorm  --no-tiled-dwconv  --no-ln-stats-epilogue  --tune-in-graph  --no-tune-orders  --tune-tail  --tune-warm  --no-efficient-batch  --efficient-batch-tol X (0)  --tune-cache PATH|auto|''\n"
               << "  --dp-backend rccl|host (rccl)  --dp-force-merge  --fail-batch-every N (fault injection, 0 = off)\n"
               << "  --http-threads N  --parse-threads N (-1 = auto, 0 = parse on the I/O threads)  --parse-spin-us N (0)  --no-batch-balance  --host ADDR (0.0.0.0)\n"
               << "  --devices 0,1,..  data parallel over these GPUs (one process each; --max-batch = whole batch);\n"

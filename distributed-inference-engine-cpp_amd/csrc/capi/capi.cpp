@@ -99,6 +99,7 @@ EngineOptions engine_opts(const Json& j) {
   e.fuse_stem_pool = jget<bool>(j, "fuse_stem_pool", e.fuse_stem_pool);
   e.fuse_gap_fc = jget<bool>(j, "fuse_gap_fc", e.fuse_gap_fc);
   e.fold_layernorm = jget<bool>(j, "fold_layernorm", e.fold_layernorm);
+  e.tiled_dwconv = jget<bool>(j, "tiled_dwconv", e.tiled_dwconv);
   e.ln_stats_epilogue = jget<bool>(j, "ln_stats_epilogue", e.ln_stats_epilogue);
   e.tune_in_graph = jget<bool>(j, "tune_in_graph", e.tune_in_graph);
   e.tune_orders = jget<bool>(j, "tune_orders", e.tune_orders);

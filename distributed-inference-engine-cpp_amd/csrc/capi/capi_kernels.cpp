@@ -359,33 +359,58 @@ int die_kern_attention_masked(uint64_t q, uint64_t k, uint64_t v, uint64_t out, 
 }
 
 // geometry JSON: B,H,W,Cin,Ho,Wo,Cout,groups,KH,KW,stride,pad_h,pad_w,dil,act,clip_lo,clip_hi,split
+static kern::GConvArgs gconv_geometry(const char* geom) {
+  Json j = Json::parse(geom);
+  kern::GConvArgs a;
+  a.B = geti(j, "B", 1);
+  a.H = geti(j, "H", 1);
+  a.W = geti(j, "W", 1);
+  a.Cin = geti(j, "Cin", 8);
+  a.Ho = geti(j, "Ho", 1);
+  a.Wo = geti(j, "Wo", 1);
+  a.Cout = geti(j, "Cout", 8);
+  a.groups = geti(j, "groups", 1);
+  a.KH = geti(j, "KH", 1);
+  a.KW = geti(j, "KW", 1);
+  a.stride = geti(j, "stride", 1);
+  a.pad_h = geti(j, "pad_h", 0);
+  a.pad_w = geti(j, "pad_w", 0);
+  a.dil = geti(j, "dil", 1);
+  a.act = geti(j, "act", 0);
+  if (auto* v = j.find("clip_lo")) a.clip_lo = static_cast<float>(v->as_double());
+  if (auto* v = j.find("clip_hi")) a.clip_hi = static_cast<float>(v->as_double());
+  a.split = geti(j, "split", 0);
+  return a;
+}
+
 int die_kern_gconv(const char* geom, uint64_t x, uint64_t w, uint64_t bias, uint64_t out, uint64_t stream) {
   try {
-    Json j = Json::parse(geom);
-    kern::GConvArgs a;
-    a.B = geti(j, "B", 1);
-    a.H = geti(j, "H", 1);
-    a.W = geti(j, "W", 1);
-    a.Cin = geti(j, "Cin", 8);
-    a.Ho = geti(j, "Ho", 1);
-    a.Wo = geti(j, "Wo", 1);
-    a.Cout = geti(j, "Cout", 8);
-    a.groups = geti(j, "groups", 1);
-    a.KH = geti(j, "KH", 1);
-    a.KW = geti(j, "KW", 1);
-    a.stride = geti(j, "stride", 1);
-    a.pad_h = geti(j, "pad_h", 0);
-    a.pad_w = geti(j, "pad_w", 0);
-    a.dil = geti(j, "dil", 1);
-    a.act = geti(j, "act", 0);
-    if (auto* v = j.find("clip_lo")) a.clip_lo = static_cast<float>(v->as_double());
-    if (auto* v = j.find("clip_hi")) a.clip_hi = static_cast<float>(v->as_double());
-    a.split = geti(j, "split", 0);
+    kern::GConvArgs a = gconv_geometry(geom);
     a.x = P<const uint16_t>(x);
     a.w = P<const float>(w);
     a.bias = P<const float>(bias);
     a.out = P<uint16_t>(out);
     return static_cast<int>(kern::grouped_conv(a, S(stream)));
+  } catch (...) {
+    return -1;
+  }
+}
+
+// Depthwise conv with the whole GConvArgs epilogue (residual, f32 output, device-side live batch
+// count) on either kernel: tiled = 1 the tiled kernel (w = fp32 [KH*KW][C]), 0 grouped_conv
+// (w = fp32 [C][KH][KW][1]).  Returns the hipError_t (1 = hipErrorInvalidValue: outside the scope).
+int die_kern_dwconv(const char* geom, int tiled, uint64_t x, uint64_t w, uint64_t bias, uint64_t res, uint64_t out,
+                    uint64_t out_f32, uint64_t live, uint64_t stream) {
+  try {
+    kern::GConvArgs a = gconv_geometry(geom);
+    a.x = P<const uint16_t>(x);
+    a.w = P<const float>(w);
+    a.bias = P<const float>(bias);
+    a.res = P<const uint16_t>(res);
+    a.out = P<uint16_t>(out);
+    a.out_f32 = P<float>(out_f32);
+    a.live = P<const long long>(live);
+    return static_cast<int>(tiled ? kern::dwconv_tiled(a, S(stream)) : kern::grouped_conv(a, S(stream)));
   } catch (...) {
     return -1;
   }
@@ -601,6 +626,14 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
       if (o.kind == PlanOp::LAYERNORM) {
         e["stats_only"] = o.stats_only != 0;
         e["rms"] = o.rms != 0;
+        e["rows"] = o.rows_per_sample;
+      }
+      if (o.kind == PlanOp::GCONV) {
+        e["tiled"] = o.tiled != 0;  // in the scope of the tiled depthwise kernel (kernels/dwconv.hip)
+        e["KH"] = o.kh;
+        e["stride"] = o.sh;
+        e["groups"] = o.groups;
+        e["residual"] = o.in2 >= 0;
       }
       if (o.kind == PlanOp::ROPE) {
         e["heads"] = o.nh;

@@ -309,6 +309,7 @@ Json engine_options_json(const EngineOptions& o) {
   j["fuse_stem_pool"] = o.fuse_stem_pool;
   j["fuse_gap_fc"] = o.fuse_gap_fc;
   j["fold_layernorm"] = o.fold_layernorm;
+  j["tiled_dwconv"] = o.tiled_dwconv;
   j["ln_stats_epilogue"] = o.ln_stats_epilogue;
   j["tune_in_graph"] = o.tune_in_graph;
   j["tune_orders"] = o.tune_orders;

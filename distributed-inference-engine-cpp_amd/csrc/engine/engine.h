@@ -249,6 +249,10 @@ struct EngineOptions {
   // ... and the statistics of a LayerNorm whose input a GEMM produces come from that GEMM's
   // epilogue (per-64-column partials, ConvArgs::stats_out / row_parts): no statistics launch
   bool ln_stats_epilogue = true;
+  // depthwise 5x5 / 7x7 stride-1 convs (PlanOp::tiled) on the LDS-tiled kernel (kernels/dwconv.hip);
+  // false: on gconv_kernel like every other grouped conv -- the same bits, for comparisons in one
+  // process (profiles/convnext.md)
+  bool tiled_dwconv = true;
   bool tune_cold = true;          // autotune with an L2 scrub before each timing (false: back-to-back)
   // after the isolated-launch autotune, time each conv's front runners in place inside eager
   // forwards (input warm from its producer, weights where the previous forward left them) and keep

@@ -1598,7 +1598,12 @@ class HipEngine : public Engine {
           g.clip_hi = op.clip_hi;
           g.split = sp_;
           g.live = live;
-          e = kern::grouped_conv(g, st);
+          if (op.tiled && opt_.tiled_dwconv) {
+            g.w = prm(op.tap_w_off);
+            e = kern::dwconv_tiled(g, st);
+          } else {
+            e = kern::grouped_conv(g, st);
+          }
           break;
         }
         case PlanOp::SOFTMAX:

@@ -57,7 +57,9 @@ struct Val {
   // holds (h, w, c); a Gemm/MatMul consumer permutes its weight rows instead of the data.
   int flat_hw = 0, flat_c = 0;
   int buf = -1;
-  int rank = 0;         // ROWS: 2 or 3
+  int rank = 0;         // ROWS: 2 or 3; 4 = Transpose(0,2,3,1) of a dense NHWC image, the same buffer read as
+                        // [N, H, W, C] rows (H * W rows of C per sample, kept in H; the image was img_h x img_w)
+  int img_h = 0, img_w = 0;
   int ld = 0, col = 0;  // ROWS/HEADS: row pitch (0 -> C) and column offset, in elements
   bool has_affine = false;
   std::vector<float> asc, ash;
@@ -138,6 +140,7 @@ class Planner {
       }
       try {
         lower(static_cast<int>(i));
+        check_output_view(n);
       } catch (const std::exception& e) {
         report_.supported = false;
         report_.unsupported.push_back(PlanReport::Item{n.name, n.op_type, e.what()});
@@ -770,12 +773,14 @@ class Planner {
   struct GemmTail {
     std::vector<float> bias;  // from a following Add(initializer), empty if none
     int act = 0;              // 1 relu, 2 gelu
-    std::string res;          // residual operand (rows)
+    std::string res;          // residual operand (rows; image = true: an NHWC image)
+    std::vector<float> colscale;  // from a following Mul(initializer [N]) (layer scale), empty if none
+    bool image = false;       // the tail went through Transpose(0,3,1,2): the output is the NHWC image of the view
     std::string out;
     std::vector<int> used;
   };
   // Epilogue fusion lookahead for a MatMul/Gemm producing `N` columns over `rows` rows per sample.
-  GemmTail gemm_tail(const Node& n, int N, int rows, bool is_gemm, int N_logical) const {
+  GemmTail gemm_tail(const Node& n, int N, int rows, bool is_gemm, int N_logical, const Val& x) const {
     GemmTail t;
     t.out = n.outputs[0];
     int c1 = sole_consumer(t.out);
@@ -787,6 +792,38 @@ class Planner {
         t.used.push_back(c1);
         t.out = m_.nodes[c1].outputs[0];
         c1 = sole_consumer(t.out);
+      }
+    }
+    // Channels-last block tail on an [N, H, W, C] view (ConvNeXt): Mul(gamma [C]), the layer scale, is
+    // folded into the GEMM's weights and bias by the caller; Transpose(0,3,1,2) -> Add(shortcut image)
+    // is the residual epilogue and the output is the NHWC image
+    if (x.kind == Val::ROWS_BF16 && x.rank == 4) {
+      if (c1 >= 0 && m_.nodes[c1].op_type == "Mul" && N_logical > 1 && is_init(other_input(m_.nodes[c1], t.out))) {
+        const auto& gm = m_.initializers.at(other_input(m_.nodes[c1], t.out));
+        if (gm.f.size() == static_cast<size_t>(N_logical) && !gm.dims.empty() && gm.dims.back() == N_logical) {
+          t.colscale = gm.f;
+          t.used.push_back(c1);
+          t.out = m_.nodes[c1].outputs[0];
+          c1 = sole_consumer(t.out);
+        }
+      }
+      if (c1 >= 0 && m_.nodes[c1].op_type == "Transpose" && m_.nodes[c1].get_ints("perm") == std::vector<int64_t>{0, 3, 1, 2}) {
+        const int c2 = sole_consumer(m_.nodes[c1].outputs[0]);
+        if (c2 >= 0 && m_.nodes[c2].op_type == "Add" && m_.nodes[c2].in(0) != m_.nodes[c2].in(1)) {
+          const std::string& other = other_input(m_.nodes[c2], m_.nodes[c1].outputs[0]);
+          auto it = vid_.find(other);
+          if (it != vid_.end()) {
+            const Val& r = vals_[it->second];
+            if (r.kind == Val::NHWC && dense(r) && r.C == N && r.logical() == N_logical && r.H == x.img_h && r.W == x.img_w) {
+              t.res = other;
+              t.image = true;
+              t.used.push_back(c1);
+              t.used.push_back(c2);
+              t.out = m_.nodes[c2].outputs[0];
+              return t;
+            }
+          }
+        }
       }
     }
     std::vector<int> gu;
@@ -902,6 +939,10 @@ class Planner {
         for (int j = 0; j < Nj; ++j) bias[offs[g] + j] = beta * c[c.size() == 1 ? 0 : j % c.size()];
       }
     }
+    // epilogue lookahead (a single GEMM only); a layer scale found there multiplies the weight columns
+    const GemmTail t = group.size() > 1 ? GemmTail{} : gemm_tail(n, Np, rows, gemm, Ntot, x);
+    for (size_t j = 0; j < t.colscale.size(); ++j)
+      for (int k = 0; k < Kpad; ++k) wp[j * Kpad + k] *= t.colscale[j];
     PlanOp p;
     p.kind = PlanOp::CONV;
     p.name = group.size() > 1 ? n.name + "+qkv" : n.name;
@@ -942,9 +983,9 @@ class Planner {
       return;
     }
 
-    const GemmTail t = gemm_tail(n, Np, rows, gemm, Ntot);
     for (int u : t.used) done_[u] = true;
     for (int j = 0; j < Np && !t.bias.empty(); ++j) bias[j] += t.bias[j];
+    for (size_t j = 0; j < t.colscale.size(); ++j) bias[j] *= t.colscale[j];
     p.bias_off = push_f32(bias);
     a.relu = t.act;
     if (!t.res.empty()) p.in2 = vals_[vid_.at(t.res)].buf;
@@ -953,7 +994,16 @@ class Planner {
     o.cl = Np != Ntot ? Ntot : 0;
     o.H = rows;
     o.rank = rank;
-    if (graph_outputs_.count(t.out) && consumers(t.out).empty() && Np == Ntot) {
+    o.img_h = x.img_h;
+    o.img_w = x.img_w;
+    if (t.image) {  // back in NCHW order: the NHWC image the view was taken of
+      p.out = new_buf(static_cast<size_t>(rows) * Np * 2);
+      o.kind = Val::NHWC;
+      o.H = x.img_h;
+      o.W = x.img_w;
+      o.rank = o.img_h = o.img_w = 0;
+      o.buf = p.out;
+    } else if (graph_outputs_.count(t.out) && consumers(t.out).empty() && Np == Ntot && rank != 4) {
       p.out_f32 = kBufGraphOut;
       o.kind = Val::ROWS_F32;
       o.buf = kBufGraphOut;
@@ -2118,7 +2168,39 @@ class Planner {
       define(n.outputs[0], o);
       return;
     }
+    // Channels-last blocks (ConvNeXt): activations are NHWC already, so NCHW -> NHWC is the same
+    // buffer read as H * W rows of C per sample, and NHWC -> NCHW of such a view is the image again
+    if (x.kind == Val::NHWC && dense(x) && perm == std::vector<int64_t>{0, 2, 3, 1}) {
+      Val o = x;
+      o.kind = Val::ROWS_BF16;
+      o.img_h = x.H;
+      o.img_w = x.W;
+      o.H = x.H * x.W;
+      o.W = 1;
+      o.rank = 4;
+      define(n.outputs[0], o);
+      return;
+    }
+    if (x.kind == Val::ROWS_BF16 && x.rank == 4 && dense(x) && perm == std::vector<int64_t>{0, 3, 1, 2}) {
+      Val o = x;
+      o.kind = Val::NHWC;
+      o.H = x.img_h;
+      o.W = x.img_w;
+      o.rank = o.img_h = o.img_w = 0;
+      define(n.outputs[0], o);
+      return;
+    }
     throw std::runtime_error("Transpose " + n.name + ": unsupported transpose for the HIP engine");
+  }
+
+  // The graph output cannot be an [N, H, W, C] rows view: the output ops write [N, C] / [N, S, C] rows
+  // or NCHW images.  Checked after each node so that the report names the node producing it.
+  void check_output_view(const Node& n) {
+    auto it = vid_.find(m_.outputs[0].name);
+    if (output_view_seen_ || it == vid_.end() || vals_[it->second].kind != Val::ROWS_BF16 || vals_[it->second].rank != 4) return;
+    output_view_seen_ = true;
+    throw std::runtime_error(n.op_type + " " + n.name + ": an [N, H, W, C] view of an image cannot be the graph output "
+                             "(transpose it back to [N, C, H, W])");
   }
 
   void lower_attn_matmul(int idx) {
@@ -2736,6 +2818,13 @@ class Planner {
                 wt.f[((static_cast<size_t>(co) * cpg + ci) * KH + ky) * KW + kx] * scale[co];
     p.w_off = push_f32(w);
     p.bias_off = push_f32(shift);
+    if (G == x.C && G == Cout && s == 1 && d == 1 && KH == KW && (KH == 5 || KH == 7)) {
+      std::vector<float> wt_tap(static_cast<size_t>(KH) * KW * Cout);
+      for (int co = 0; co < Cout; ++co)
+        for (int tap = 0; tap < KH * KW; ++tap) wt_tap[static_cast<size_t>(tap) * Cout + co] = w[static_cast<size_t>(co) * KH * KW + tap];
+      p.tiled = 1;
+      p.tap_w_off = push_f32(wt_tap);
+    }
     p.groups = G;
     p.C = x.C;
     p.H = x.H;
@@ -2824,8 +2913,20 @@ class Planner {
     bool ok;
     const int64_t axis = last_axis_of(n, m_, ok);
     const int rank = x.rank ? x.rank : 2;
-    if (!ok || !(axis == -1 || axis == rank - 1)) fail("reduction over the last axis with keepdims");
-    if (x.kind != Val::ROWS_BF16 || x.pitch() != x.C || x.col) fail("input must be dense rows");
+    // over axis 1 of an NCHW image (channels-first LayerNorm of older ConvNeXt exports): the channel
+    // axis is the last one of the stored NHWC pixels, so it is the same op on the image's H * W rows
+    const bool image = x.kind == Val::NHWC;
+    if (image && !(ok && (axis == 1 || axis == -3))) fail("on an image, reduction over the channel axis with keepdims");
+    if (!image && (!ok || !(axis == -1 || axis == rank - 1))) fail("reduction over the last axis with keepdims");
+    if (!(x.kind == Val::ROWS_BF16 || image) || x.pitch() != x.C || x.col) fail("input must be dense rows");
+    // gamma / beta: [C] on rows, [C, 1, 1] (broadcast over the pixels) on an image
+    auto affine_init = [&](const std::string& nm) {
+      auto it = m_.initializers.find(nm);
+      if (it == m_.initializers.end() || static_cast<int>(it->second.f.size()) != x.C) return false;
+      const auto& d = it->second.dims;
+      if (!image) return true;
+      return (d.size() == 3 || d.size() == 4) && d[d.size() - 3] == x.C;
+    };
     const std::string& xn = n.in(0);
     const std::string& mu = n.outputs[0];
     int sub = -1;
@@ -2856,15 +2957,13 @@ class Planner {
     std::string cur = m_.nodes[div].outputs[0];
     std::vector<int> used = {sub, sq, rm2, add, sq_rt, div};
     int c = sole_consumer(cur);
-    if (c >= 0 && m_.nodes[c].op_type == "Mul" && is_init(other_input(m_.nodes[c], cur)) &&
-        static_cast<int>(m_.initializers.at(other_input(m_.nodes[c], cur)).f.size()) == x.C) {
+    if (c >= 0 && m_.nodes[c].op_type == "Mul" && affine_init(other_input(m_.nodes[c], cur))) {
       g = m_.initializers.at(other_input(m_.nodes[c], cur)).f;
       used.push_back(c);
       cur = m_.nodes[c].outputs[0];
       c = sole_consumer(cur);
     }
-    if (c >= 0 && m_.nodes[c].op_type == "Add" && is_init(other_input(m_.nodes[c], cur)) &&
-        static_cast<int>(m_.initializers.at(other_input(m_.nodes[c], cur)).f.size()) == x.C) {
+    if (c >= 0 && m_.nodes[c].op_type == "Add" && affine_init(other_input(m_.nodes[c], cur))) {
       b = m_.initializers.at(other_input(m_.nodes[c], cur)).f;
       used.push_back(c);
       cur = m_.nodes[c].outputs[0];
@@ -3630,6 +3729,7 @@ class Planner {
   std::unordered_map<std::string, int> prepped_;
   std::unordered_map<std::string, std::array<int64_t, 4>> folded_pad_;  // Pad output -> (t, l, b, r) for its conv
   std::vector<bool> done_;
+  bool output_view_seen_ = false;
 };
 
 }  // namespace

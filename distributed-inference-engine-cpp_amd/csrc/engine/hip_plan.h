@@ -66,6 +66,15 @@
 //    Mul(x, Reciprocal(.)) / Mul(x, Div(1, .)) [-> Mul(weight [C])], and the single nodes
 //    RMSNormalization / SimplifiedLayerNormalization, are a LAYERNORM op with rms = 1 (never folded
 //    into its GEMM readers).
+//  * channels-last blocks (ConvNeXt): Transpose(0,2,3,1) of a dense NHWC image is the same buffer read
+//    as an [N, H, W, C] rows view (no op, no copy), on which LayerNormalization over the last axis,
+//    MatMul with a [C, N] initializer + bias Add and the erf-GELU chain take the rows lowerings;
+//    Transpose(0,3,1,2) of such a view is the image again, and behind a GEMM the Add of the shortcut
+//    image after it is that GEMM's residual epilogue.  Mul(GEMM output, gamma [C]) with no other reader
+//    of the GEMM (layer scale) is folded into its weights and bias.  The decomposed LayerNorm over
+//    axis 1 of an NCHW image is the LAYERNORM op over the image's rows.  Depthwise 5x5 / 7x7 stride-1
+//    convs are marked for the tiled kernel (PlanOp::tiled).  Rejected with a report line: other 4-D
+//    permutes of an image, the view as the graph output, a LayerNorm over any other axis.
 // Anything else falls back to standalone affine/add/relu kernels, or is rejected with a clear
 // error (the CPU executor still runs such models).
 #pragma once
@@ -154,6 +163,11 @@ struct PlanOp {
   // BF16_TO_F32 / TO_NCHW_F32 drop the pad columns, SOFTMAX reads and writes rows of this pitch
   int ld_store = 0;
   int groups = 1;                      // GCONV
+  // GCONV in the scope of the tiled depthwise kernel (kern::dwconv_tiled: depthwise, stride 1,
+  // dilation 1, 5x5 / 7x7): tiled = 1 and tap_w_off = the same weights as fp32 [tap][C]; the engine
+  // picks the kernel (EngineOptions::tiled_dwconv), w_off stays valid for kern::grouped_conv
+  int tiled = 0;
+  size_t tap_w_off = SIZE_MAX;
   float clip_lo = 0.f, clip_hi = 0.f;  // act == 3 (Clip) of AFFINE / GCONV
   long long rows_per_sample = 0;  // AFFINE / LAYERNORM: rows of C per sample
   // transformer ops: sequence length, heads, head dim, column offsets / pitches of in/in2/in3

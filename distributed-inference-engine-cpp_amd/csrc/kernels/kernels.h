@@ -175,6 +175,11 @@ struct GConvArgs {
   const long long* live = nullptr;
 };
 hipError_t grouped_conv(const GConvArgs& a, hipStream_t s);
+// Tiled depthwise convolution (dwconv.hip): the same arguments and epilogue, but w = fp32 [KH*KW][C]
+// (tap-major).  Scope: groups == Cin == Cout, C % 8 == 0, stride 1, dilation 1, 5x5 / 7x7, pads >= 0;
+// anything else returns hipErrorInvalidValue and launches nothing.  Same bits as grouped_conv.
+bool dwconv_tiled_supported(const GConvArgs& a);
+hipError_t dwconv_tiled(const GConvArgs& a, hipStream_t s);
 
 // Softmax over the last axis of [rows][C] (one wave per row, fp32 math); writes bf16/split `y`
 // (row pitch ld) and/or f32 `y_f32` (dense [rows][C]).  ld = stored row pitch of x and y (0 = C).

@@ -756,6 +756,8 @@ def _sig_kernels():
     L.die_kern_stem_nchw.argtypes = [u64, i] + [u64] * 5 + [i] * 6 + [u64, i, i]
     L.die_kern_gconv.restype = i
     L.die_kern_gconv.argtypes = [C.c_char_p] + [u64] * 5
+    L.die_kern_dwconv.restype = i
+    L.die_kern_dwconv.argtypes = [C.c_char_p, i] + [u64] * 8
     L.die_kern_softmax.restype = i
     L.die_kern_softmax.argtypes = [u64, u64, u64, C.c_longlong, i, u64, i]
     L.die_kern_layernorm.restype = i

@@ -858,6 +858,49 @@ def grouped_conv(x_nhwc, w, bias=None, stride=1, pads=(0, 0, 0, 0), groups=1, cl
     return _out(out, split)
 
 
+def depthwise_conv(x_nhwc, w, bias=None, pads=(0, 0, 0, 0), stride=1, dilation=1, clip=None, relu=False, residual=None,
+                   split=False, want_f32=False, live=None, fill=None, tiled=True, groups=None):
+    """Depthwise conv with the whole epilogue, on the tiled kernel (csrc/kernels/dwconv.hip; tiled=False:
+    the same call on gconv_kernel, for comparison).  x [B,H,W,C] (bf16, or any float dtype with split),
+    w [C,1,k,k] float, pads [top, left, bottom, right], residual [B,Ho,Wo,C] added after the activation,
+    live: number of leading samples to compute (a device-side count; the others keep `fill`).
+    Returns (stored planes: bf16 [B,Ho,Wo,C], or [2,B,Ho,Wo,C] hi / lo when split; f32 output or None).
+    A geometry outside the tiled kernel's scope raises NativeError with hipError 1 and launches nothing."""
+    import torch
+
+    B, H, W, C = x_nhwc.shape
+    Cout, cpg, KH, KW = w.shape
+    Ho = (H + pads[0] + pads[2] - dilation * (KH - 1) - 1) // stride + 1
+    Wo = (W + pads[1] + pads[3] - dilation * (KW - 1) - 1) // stride + 1
+    dev = x_nhwc.device
+    xin = _in(x_nhwc, split) if split else x_nhwc.to(torch.bfloat16).contiguous()
+    if tiled:  # [tap][C]
+        wp = w.float().reshape(Cout, cpg * KH * KW).t().contiguous()
+    else:
+        wp = w.float().permute(0, 2, 3, 1).contiguous()
+    bp = None if bias is None else bias.float().contiguous()
+    rp = None
+    if residual is not None:
+        rp = _in(residual, split) if split else residual.to(torch.bfloat16).contiguous()
+    shape = ((2,) if split else ()) + (B, Ho, Wo, Cout)
+    out = torch.empty(shape, dtype=torch.bfloat16, device=dev)
+    of = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32, device=dev) if want_f32 else None
+    if fill is not None:
+        out.fill_(fill)
+        if of is not None:
+            of.fill_(fill)
+    lv = None if live is None else torch.tensor([int(live)], dtype=torch.int64, device=dev)
+    act = 3 if clip is not None else (1 if relu else 0)
+    lo, hi = clip if clip is not None else (0.0, 0.0)
+    geom = dict(B=B, H=H, W=W, Cin=C, Ho=Ho, Wo=Wo, Cout=Cout, groups=C if groups is None else groups, KH=KH, KW=KW,
+                stride=stride, dil=dilation, pad_h=pads[0], pad_w=pads[1], act=act, clip_lo=float(lo), clip_hi=float(hi),
+                split=int(split))
+    rc = native.kernels().die_kern_dwconv(json.dumps(geom).encode(), int(tiled), _ptr(xin), _ptr(wp), _ptr(bp), _ptr(rp),
+                                          _ptr(out), _ptr(of), _ptr(lv), _stream())
+    _check(rc, "depthwise_conv")
+    return out, of
+
+
 def softmax_rows(x, split=False):
     """x [rows, C] float -> (softmax stored bf16/split -> fp32 values, softmax fp32)."""
     import torch

@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=["resnet50", "vit_b16"], default="resnet50")
+    ap.add_argument("--arch", choices=["resnet50", "vit_b16", "convnext_tiny"], default="resnet50")
     ap.add_argument("--lo", type=int, default=12)
     ap.add_argument("--hi", type=int, default=32)
     ap.add_argument("--iters", type=int, default=40)
@@ -22,6 +22,7 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--no-fuse-pairs", action="store_true", help="EngineOptions::fuse_pairs off")
     ap.add_argument("--tune-tail", action="store_true", help="EngineOptions::tune_tail on")
+    ap.add_argument("--no-tiled-dwconv", action="store_true", help="EngineOptions::tiled_dwconv off")
     ap.add_argument("--pair-shared-w", type=int, default=-2,
                     help="measurement: force PairArgs::shared_w for every pair launch (-1 auto, 0 never, 1 always)")
     a = ap.parse_args()
@@ -35,6 +36,10 @@ def main():
         from die_amd.models import vit as m
 
         cfg = m.ViTConfig()
+    elif a.arch == "convnext_tiny":  # ConvNeXt-T
+        from die_amd.models import convnext as m
+
+        cfg = m.ConvNeXtConfig()
     else:
         from die_amd.models import resnet_v2 as m
 
@@ -43,7 +48,7 @@ def main():
     path = os.path.join(tempfile.mkdtemp(), a.arch + ".onnx")
     open(path, "wb").write(m.build_onnx(cfg)[0])
     e = native.Engine(path, device="hip", max_batch=a.hi, precision=a.precision,
-                      fuse_pairs=not a.no_fuse_pairs, tune_tail=a.tune_tail)
+                      fuse_pairs=not a.no_fuse_pairs, tune_tail=a.tune_tail, tiled_dwconv=not a.no_tiled_dwconv)
     x = m.synthetic_input(a.hi, cfg, seed=3).reshape(a.hi, -1).astype(np.float32)
     rows = []
     for B in range(a.lo, a.hi + 1):
@@ -60,7 +65,7 @@ def main():
     buckets = e.refresh_info().get("buckets")
     e.close()
     lines = ["# %s %s%s: captured-forward device time per batch size" % (
-        a.arch, a.precision, (", unfused pairs" if a.no_fuse_pairs else "") + (", tail split-K tuned" if a.tune_tail else "") + (
+        a.arch, a.precision, (", unfused pairs" if a.no_fuse_pairs else "") + (", tail split-K tuned" if a.tune_tail else "") + (", gconv depthwise" if a.no_tiled_dwconv else "") + (
             ", pair shared_w %d" % a.pair_shared_w if a.pair_shared_w >= -1 else "")), "",
              "Graph buckets: %s." % buckets, "", "| batch | device ms | us / image |", "|---:|---:|---:|"]
     lines += ["| %d | %.3f | %.1f |" % (r["batch"], r["device_ms"], r["us_per_image"]) for r in rows]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-op device time of one forward on the HIP engine (events around eager launches of the tuned
-kernels), written as a markdown table + JSON.  Usage: op_profile.py --arch resnet50|vit_b16 --batch 32
+kernels), written as a markdown table + JSON.  Usage: op_profile.py --arch resnet50|vit_b16|convnext_tiny --batch 32
 Token-id models (--arch bert_ids|bert_ids_hf|sbert_ids|sbert_ids_hf|sbert_cls) are profiled on a batch of ids fed first: --ids full
 (every sequence full length) or synthetic (models/generic.py synthetic lengths and holes)."""
 import argparse
@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--arch", choices=["resnet50", "vit_b16", "bert_ids", "bert_ids_hf", "sbert_ids", "sbert_ids_hf", "sbert_cls"], default="resnet50")
+    ap.add_argument("--arch", choices=["resnet50", "vit_b16", "convnext_tiny", "bert_ids", "bert_ids_hf", "sbert_ids", "sbert_ids_hf", "sbert_cls"], default="resnet50")
     ap.add_argument("--ids", choices=["full", "synthetic"], default="full", help="token-id models: the profiled batch")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--iters", type=int, default=20)
@@ -34,6 +34,8 @@ def main():
     ap.add_argument("--no-ln-stats-epilogue", action="store_true",
                     help="LayerNorm statistics launches instead of producer-epilogue partials (EngineOptions::ln_stats_epilogue)")
     ap.add_argument("--fuse-gap-fc", action="store_true", help="global pool and FC head as one launch (EngineOptions::fuse_gap_fc)")
+    ap.add_argument("--no-tiled-dwconv", action="store_true",
+                    help="5x5 / 7x7 depthwise convs on gconv_kernel, not the tiled kernel (EngineOptions::tiled_dwconv)")
     ap.add_argument("--no-fuse-stem-pool", action="store_true", help="stem and max pool as two launches (EngineOptions::fuse_stem_pool)")
     a = ap.parse_args()
     import torch  # noqa: F401  (one HIP runtime)
@@ -50,6 +52,10 @@ def main():
         from die_amd.models import vit as m
 
         cfg = m.ViTConfig()
+    elif a.arch == "convnext_tiny":  # ConvNeXt-T
+        from die_amd.models import convnext as m
+
+        cfg = m.ConvNeXtConfig()
     else:
         from die_amd.models import resnet_v2 as m
 
@@ -63,7 +69,7 @@ def main():
                       splitk_fused_margin=a.splitk_fused_margin, splitk_two_kernel=a.splitk_two_kernel,
                       fuse_stem_pool=not a.no_fuse_stem_pool, fuse_gap_fc=a.fuse_gap_fc, fold_layernorm=not a.no_fold_layernorm,
                       ln_stats_epilogue=not a.no_ln_stats_epilogue, tune_in_graph=a.tune_in_graph, conv_order=a.conv_order,
-                      tune_orders=not a.no_tune_orders, tune_tail=a.tune_tail,
+                      tune_orders=not a.no_tune_orders, tune_tail=a.tune_tail, tiled_dwconv=not a.no_tiled_dwconv,
                       **({"pipeline_depth": 1} if token_ids else {}),
                       **({} if a.tune_streamk < 0 else {"tune_streamk": bool(a.tune_streamk)}))
     if token_ids:  # one pipeline slot: the profiled forwards read the ids this run leaves in it
