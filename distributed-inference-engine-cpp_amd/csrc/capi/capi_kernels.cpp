@@ -3,6 +3,7 @@
 // and torch.cuda.current_stream().cuda_stream).
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -29,6 +30,97 @@ char* dup(const std::string& s) {
   char* p = static_cast<char*>(std::malloc(s.size() + 1));
   std::memcpy(p, s.data(), s.size() + 1);
   return p;
+}
+
+// The whole of a plan as text, for "same plan" checks (tools/plan_dump.py): one line per op with every
+// PlanOp member (for `conv` every non-pointer ConvArgs member), one per buffer, the plan's scalars and
+// a 64-bit FNV-1a of the parameter blob.  Floats print with 9 significant digits (exact for fp32),
+// doubles with 17; an offset of SIZE_MAX prints as -1.
+struct DumpLine {
+  std::string s;
+  char tmp[64];
+  DumpLine& str(const char* k, const std::string& v) { return s += std::string(" ") + k + "=" + v, *this; }
+  DumpLine& i(const char* k, long long v) { return str(k, std::to_string(v)); }
+  DumpLine& off(const char* k, size_t v) { return i(k, v == SIZE_MAX ? -1 : static_cast<long long>(v)); }
+  DumpLine& f(const char* k, float v) { return std::snprintf(tmp, sizeof tmp, "%.9g", static_cast<double>(v)), str(k, tmp); }
+  DumpLine& d(const char* k, double v) { return std::snprintf(tmp, sizeof tmp, "%.17g", v), str(k, tmp); }
+};
+
+std::string plan_dump(const Plan& p) {
+  std::string out;
+  for (const PlanOp& o : p.ops) {
+    DumpLine l;
+    l.s = "op";
+    l.i("kind", o.kind).str("name", o.name);
+    l.i("in", o.in).i("in2", o.in2).i("in3", o.in3).i("in4", o.in4).i("in5", o.in5);
+    l.i("out", o.out).i("out2", o.out2).i("out3", o.out3).i("out_f32", o.out_f32).i("out_stats", o.out_stats);
+    l.off("w_off", o.w_off).off("bias_off", o.bias_off).off("s2_off", o.s2_off).off("b2_off", o.b2_off);
+    l.off("scale_off", o.scale_off).off("shift_off", o.shift_off).off("tap_w_off", o.tap_w_off);
+    l.off("type_off", o.type_off).off("w2_off", o.w2_off).off("bias2_off", o.bias2_off).off("colsum_off", o.colsum_off);
+    const kern::ConvArgs& a = o.conv;
+    l.i("conv.B", a.B).i("conv.H", a.H).i("conv.W", a.W).i("conv.Cin", a.Cin).i("conv.Ho", a.Ho).i("conv.Wo", a.Wo);
+    l.i("conv.N", a.N).i("conv.KH", a.KH).i("conv.KW", a.KW).i("conv.stride", a.stride).i("conv.pad_h", a.pad_h);
+    l.i("conv.pad_w", a.pad_w).i("conv.dil", a.dil).i("conv.K", a.K).i("conv.Kpad", a.Kpad).i("conv.M", a.M);
+    l.i("conv.relu", a.relu).i("conv.relu2", a.relu2).i("conv.splits", a.splits).i("conv.counters_n", a.counters_n);
+    l.f("conv.clip_lo", a.clip_lo).f("conv.clip_hi", a.clip_hi).f("conv.ln_eps", a.ln_eps).i("conv.split", a.split);
+    l.i("conv.wplane", a.wplane).i("conv.xplane", a.xplane).i("conv.oplane", a.oplane).i("conv.order", a.order);
+    l.i("conv.probe", a.probe).i("conv.tail", a.tail).i("conv.sk", a.sk);
+    l.i("tile_bmax", o.tile_bmax).i("C", o.C).i("H", o.H).i("W", o.W).i("Ho", o.Ho).i("Wo", o.Wo).i("Cp", o.Cp);
+    l.i("kh", o.kh).i("kw", o.kw).i("sh", o.sh).i("sw", o.sw).i("ph", o.ph).i("pw", o.pw).i("is_max", o.is_max);
+    l.i("cip", o.cip).i("act", o.act).i("ld_store", o.ld_store).i("groups", o.groups).i("tiled", o.tiled);
+    l.f("clip_lo", o.clip_lo).f("clip_hi", o.clip_hi).i("rows_per_sample", o.rows_per_sample);
+    l.i("S", o.S).i("nh", o.nh).i("hd", o.hd).i("gidx", o.gidx);
+    for (int r = 0; r < 3; ++r) l.i(("col" + std::to_string(r)).c_str(), o.col[r]).i(("ld" + std::to_string(r)).c_str(), o.ld[r]);
+    l.f("fscale", o.fscale).f("eps", o.eps).i("bias_heads", o.bias_heads).i("causal", o.causal);
+    l.i("key_mask", o.key_mask).i("kv_heads", o.kv_heads);
+    l.i("pad.op", o.pad.op).f("pad.value", o.pad.value).i("pad.negated", o.pad.negated);
+    l.i("pad.truncated", o.pad.truncated).i("pad.src", o.pad.src);
+    l.i("in_ld", o.in_ld).i("seg_ids", o.seg_ids).i("seg_types", o.seg_types).i("type_rows", o.type_rows);
+    l.i("normalize", o.normalize).f("count_min", o.count_min).d("flops", o.flops_per_sample).i("join", o.join);
+    l.i("w2plane", o.w2plane).i("n2", o.n2).i("pair_relu", o.pair_relu).i("stats_only", o.stats_only).i("rms", o.rms);
+    l.i("in3_parts", o.in3_parts);
+    out += l.s + "\n";
+  }
+  for (const PlanBuf& b : p.bufs) {
+    DumpLine l;
+    l.s = "buf";
+    l.i("bytes_per_sample", static_cast<long long>(b.bytes_per_sample)).i("offset", static_cast<long long>(b.offset));
+    l.i("first_use", b.first_use).i("last_use", b.last_use);
+    out += l.s + "\n";
+  }
+  DumpLine l;
+  l.s = "plan";
+  l.i("arena_bytes_per_sample", static_cast<long long>(p.arena_bytes_per_sample));
+  l.i("arena_bytes", static_cast<long long>(p.arena_bytes));
+  l.i("input_numel", static_cast<long long>(p.input_numel)).i("output_numel", static_cast<long long>(p.output_numel));
+  l.d("flops", p.flops_per_sample).i("split", p.split);
+  std::string shape;
+  for (auto v : p.input_shape) shape += (shape.empty() ? "" : ",") + std::to_string(v);
+  l.str("input_shape", shape);
+  shape.clear();
+  for (auto v : p.output_shape) shape += (shape.empty() ? "" : ",") + std::to_string(v);
+  l.str("output_shape", shape);
+  for (const auto& s : p.inputs)
+    l.str("input", s.name + ":" + s.role + ":" + std::to_string(s.offset) + ":" + std::to_string(s.numel));
+  uint64_t h = 14695981039346656037ull;
+  for (uint8_t b : p.params) h = (h ^ b) * 1099511628211ull;
+  std::snprintf(l.tmp, sizeof l.tmp, "%016llx", static_cast<unsigned long long>(h));
+  l.i("param_bytes", static_cast<long long>(p.params.size())).str("params_fnv1a", l.tmp);
+  return out + l.s + "\n";
+}
+
+// fuse: bit 0 conv pairs, bit 1 stem + pool, bit 2 global pool + FC head, bit 3 LayerNorm folding,
+// bit 4 LayerNorm statistics from the producing GEMM's epilogue
+PlanOptions plan_options(int side_branches, int split, int fuse) {
+  PlanOptions po;
+  po.side_branches = side_branches != 0;
+  po.split = split != 0;
+  po.fuse_pairs = (fuse & 1) != 0;
+  po.fuse_stem_pool = (fuse & 2) != 0;
+  po.fuse_gap_fc = (fuse & 4) != 0;
+  po.fold_layernorm = (fuse & 8) != 0;
+  po.ln_stats_epilogue = (fuse & 16) != 0;
+  return po;
 }
 }  // namespace
 
@@ -505,19 +597,20 @@ char* die_hybrid_partition(const char* model_path, int max_batch, int split, cha
   }
 }
 
-// fuse: bit 0 conv pairs, bit 1 stem + pool, bit 2 global pool + FC head, bit 3 LayerNorm folding,
-// bit 4 LayerNorm statistics from the producing GEMM's epilogue
+// Every member of a model's plan as text (plan_dump above); the arguments of die_plan_summary.
+char* die_plan_dump(const char* model_path, int max_batch, int side_branches, int split, int fuse, char** err) {
+  try {
+    return dup(plan_dump(build_plan(onnx::load_onnx(model_path), max_batch, plan_options(side_branches, split, fuse))));
+  } catch (const std::exception& e) {
+    if (err) *err = dup(e.what());
+    return nullptr;
+  }
+}
+
+// fuse: the bits of plan_options
 char* die_plan_summary(const char* model_path, int max_batch, int side_branches, int split, int fuse, char** err) {
   try {
-    PlanOptions po;
-    po.side_branches = side_branches != 0;
-    po.split = split != 0;
-    po.fuse_pairs = (fuse & 1) != 0;
-    po.fuse_stem_pool = (fuse & 2) != 0;
-    po.fuse_gap_fc = (fuse & 4) != 0;
-    po.fold_layernorm = (fuse & 8) != 0;
-    po.ln_stats_epilogue = (fuse & 16) != 0;
-    Plan p = build_plan(onnx::load_onnx(model_path), max_batch, po);
+    Plan p = build_plan(onnx::load_onnx(model_path), max_batch, plan_options(side_branches, split, fuse));
     Json j = Json::object();
     j["summary"] = p.summary();
     j["arena_bytes"] = static_cast<long long>(p.arena_bytes);
@@ -527,12 +620,7 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
     Json ops = Json::array();
     for (auto& o : p.ops) {
       Json e = Json::object();
-      static const char* kinds[] = {"input_prep", "conv", "pool", "gap", "affine", "to_nchw_f32", "bf16_to_f32",
-                                    "layernorm", "tokens", "gather_rows", "attention", "stem", "gconv", "softmax",
-                                    "rows_prep", "copy_cols", "binary", "unary", "conv_pair", "pad", "where", "resize", "bmm", "gap_fc",
-                                    "embed_tokens", "pool_tokens", "rope"};
-      static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::ROPE + 1, "one name per PlanOp kind");
-      e["kind"] = kinds[o.kind];
+      e["kind"] = plan_kind_name(o.kind);
       e["name"] = o.name;
       e["gflop"] = o.flops_per_sample / 1e9;
       e["join"] = o.join;

@@ -1,82 +1,19 @@
-// Lowering of an ONNX graph to a fused, NHWC/bf16 device program for gfx950.
-//
-// Passes (one walk over the topologically sorted nodes, with lookahead):
-//  * BatchNormalization directly on the graph input -> folded into the input-prep kernel that also
-//    converts NCHW fp32 -> NHWC bf16 (it cannot be folded into the stem weights exactly, because the
-//    stem's zero padding is applied after the BN);
-//  * Conv -> BatchNormalization -> Relu  -> one conv with folded weights/bias and ReLU epilogue;
-//  * Conv -> Add(other) [-> Relu]        -> residual epilogue (other operand already computed);
-//  * value -> BatchNormalization [-> Relu] consumed next to the value itself (pre-activation units)
-//    -> the producing conv's second output (dual store), so ResNet-v2 has no standalone BN/ReLU/Add;
-//  * Gemm / MatMul(2-D initializer) -> the same MFMA kernel as a 1x1 conv over rows;
-//  * GlobalAveragePool / MaxPool / AveragePool -> NHWC kernels; Flatten of 1x1 maps -> view.
-//  * transformers (ViT): the patch Conv's Reshape/Transpose, the heads Reshape/Transpose, the
-//    MatMul -> Div -> Softmax -> MatMul chain and the shape-computation subgraph are all lazy views;
-//    the chain materialises as one fused attention kernel when the context is merged back into rows.
-//    Between Q K^T and the Softmax the chain also takes, in any number and order, Add(scores, B)
-//    with a float initializer B and Where(C, scores, f) / Where(C, f, scores) with a bool
-//    initializer C and a scalar fill f <= -1e4 (taken as -inf), B / C broadcastable to
-//    [1, nh, S, S] (rank 2 to 4, leading dims 1 or nh, last two (S, S), (1, S) or (S, 1)).  They
-//    fold into one additive table per attention (a later scale multiplies it, Adds sum), which is
-//    classified: a -inf strict upper triangle becomes the kernel's causal flag, equal heads one
-//    shared slice, an all-zero remainder no table at all (causal masks, relative-position / ALiBi
-//    tables, BERT key masks, sliding windows).  Rejected with a report line: shapes that do not
-//    broadcast, a finite fill above -1e4, a query row with no visible key, and a mask that is not an
-//    initializer -- folding of mask-building Slice / Cast subgraphs, cross-attention and KV caches
-//    are out of scope.
-//    Sibling Q/K/V MatMuls become one GEMM (N = 3*D); MatMul -> Add(bias) -> erf-GELU and
-//    MatMul -> Add(bias) -> Add(residual) fold into the GEMM epilogue; cls Expand/Concat + position
-//    Add -> one token-assembly kernel; LayerNormalization and Gather(token) -> row kernels.
-//  * token-id models: a rank-2 input [N, S] whose consumers all treat it as ids (Cast to an integer
-//    type, Gather indices, Equal / Greater / Less against a scalar) gets no ROWS_PREP;
-//    Gather(table, ids, axis 0) [+ Add(positions)] [+ Add(token-type row)] is one EMBED_TOKENS op
-//    reading the fp32 input in place, and a padding mask derived from the ids (a pad test through
-//    Not / Cast / Unsqueeze / Reshape / Sub(1, m) / Mul(m, c <= -1e4)) consumed on attention scores
-//    as Where(vis, scores, f), Where(hidden, f, scores) or Add(scores, additive) becomes the
-//    attention op's key_mask flag: EMBED_TOKENS writes the per-sample key data once per forward.
-//    Rejected with a report line: key mask + causal, a visibility value used in any other way,
-//    Gather on another axis or from a non-initializer table, mask shapes other than
-//    [N, 1, 1, S].
-//  * attention_mask / token_type_ids graph inputs: 2 or 3 rank-2 inputs [N, S] with one S, declared
-//    FLOAT / INT64 / INT32 in any order; a request row is their concatenation in declaration order
-//    and is read in place.  Roles come from use: an input that only indexes Gather(initializer
-//    [V, D], ., axis 0) is ids or types (the earlier-declared of two is the ids), and the two lookups,
-//    summed by Add with each other and the position Add in any order, are one EMBED_TOKENS op (a
-//    constant type row and a type input exclude each other); an input that is a visibility value
-//    roots the key-mask machinery above as the pad test "value != 0" read from the mask segment
-//    (values other than 0 / 1 are outside the contract: non-zero is visible).  Rejected with a
-//    report line naming the input: different S or rank, more than 3 inputs, an input that is
-//    neither, one used both ways, a second input on a model without token ids; a mask input plus a
-//    different ids-derived pad test is two pad tests.  Such a model is never partitioned.
-//  * sentence embedders: the masked mean over the tokens, Mul(rows, m) -> ReduceSum(axis 1) divided by
-//    ReduceSum(m, axis 1) [-> Clip(min) / Max] with m = the same visibility value unsqueezed at the
-//    last axis [-> Expand to [N, S, D]] -> Cast, is one POOL_TOKENS op reading the key data; an L2
-//    normalisation of rank-2 rows over the last axis (LpNormalization p = 2, or torch's F.normalize
-//    export ReduceL2 -> Clip(min = eps) -> [Expand] -> Div) joins that op when the pooled vector has
-//    no other reader and is a POOL_TOKENS op with S = 1 anywhere else.  As the graph output the op
-//    writes fp32 straight into the output buffer.  Sum / max / last-token pooling: out of scope.
-//  * rotary position embeddings: on a heads view x ([N, H, S, hd] after the head transpose, or
-//    [N, S, H, hd] before it) the seven nodes Mul(x, COS), Slice(x, 0:hd/2), Slice(x, hd/2:hd), Neg,
-//    Concat([-hi, lo]), Mul(., SIN), Add are one ROPE op with the two float initializers as [S][hd]
-//    tables; its output is a heads view on a new dense rows buffer, so the attention lowering is
-//    unchanged (one launch each for Q and K).  Rejected with a report line: halves that do not meet
-//    at hd/2 or a step != 1 (interleaved), rotation of fewer than hd columns (partial), tables that
-//    are not initializers or do not broadcast over [S, hd], a head dim attention does not take.
-//  * RMSNorm: Pow(x, 2) / Mul(x, x) -> ReduceMean(-1) -> Add(eps) -> Sqrt -> Div(x, .) /
-//    Mul(x, Reciprocal(.)) / Mul(x, Div(1, .)) [-> Mul(weight [C])], and the single nodes
-//    RMSNormalization / SimplifiedLayerNormalization, are a LAYERNORM op with rms = 1 (never folded
-//    into its GEMM readers).
-//  * channels-last blocks (ConvNeXt): Transpose(0,2,3,1) of a dense NHWC image is the same buffer read
-//    as an [N, H, W, C] rows view (no op, no copy), on which LayerNormalization over the last axis,
-//    MatMul with a [C, N] initializer + bias Add and the erf-GELU chain take the rows lowerings;
-//    Transpose(0,3,1,2) of such a view is the image again, and behind a GEMM the Add of the shortcut
-//    image after it is that GEMM's residual epilogue.  Mul(GEMM output, gamma [C]) with no other reader
-//    of the GEMM (layer scale) is folded into its weights and bias.  The decomposed LayerNorm over
-//    axis 1 of an NCHW image is the LAYERNORM op over the image's rows.  Depthwise 5x5 / 7x7 stride-1
-//    convs are marked for the tiled kernel (PlanOp::tiled).  Rejected with a report line: other 4-D
-//    permutes of an image, the view as the graph output, a LayerNorm over any other axis.
-// Anything else falls back to standalone affine/add/relu kernels, or is rejected with a clear
-// error (the CPU executor still runs such models).
+// Lowering of an ONNX graph to a fused, NHWC/bf16 device program for gfx950: one walk over the
+// topologically sorted nodes, with lookahead (Planner, engine/planner.h), then the post-lowering
+// passes (engine/plan_passes.h).  What each family of nodes lowers to, and what is rejected with a
+// report line, is described at the head of the file that implements it:
+//  * hip_plan.cpp             the walk, the dispatch by operand kind and op type, graph inputs / output
+//  * plan_lower_image.cpp     convs with their BN / ReLU / residual / dual-store epilogues, pools, pads,
+//                             Resize, channels-last blocks (ConvNeXt)
+//  * plan_lower_gemm.cpp      Gemm / MatMul(initializer) with bias, GELU and residual epilogues, Q/K/V merge
+//  * plan_lower_attention.cpp head views, the attention chain with folded biases / masks, repeat_kv
+//                             (grouped-query attention), rotary position embeddings
+//  * plan_lower_tokens.cpp    token-id models, attention_mask / token_type_ids inputs, sentence pooling,
+//                             ViT token assembly
+//  * plan_lower_norm.cpp      LayerNormalization, RMSNorm and their decomposed exports
+//  * plan_lower_general.cpp   everything else: standalone unary / binary / compare / Where / concat / slice
+// Anything the planner cannot lower is rejected with a clear error (the CPU executor still runs such
+// models).
 #pragma once
 
 #include <cstdint>
@@ -237,6 +174,9 @@ struct Plan {
   bool split = false;
   std::string summary() const;
 };
+
+// "conv", "layernorm", ...: the name of an op kind in summaries and profiles
+const char* plan_kind_name(PlanOp::Kind kind);
 
 // Thrown by build_plan for a graph with nodes the HIP planner cannot lower (what() lists them all):
 // the engine factory's cue for the hybrid HIP + CPU partition (engine.cpp create_engine).

@@ -833,6 +833,26 @@ def plan_summary(model_path: str, max_batch: int = 32, side_branches: bool = Fal
     return json.loads(_take_str(p))
 
 
+def plan_dump(model_path: str, max_batch: int = 32, side_branches: bool = False,
+              precision: str = "bf16", fuse_pairs: bool = True, fuse_stem_pool: bool = True,
+              fuse_gap_fc: bool = False, fold_layernorm: bool = True,
+              ln_stats_epilogue: bool = True) -> str:
+    """The whole plan as text, for identity checks (tools/plan_dump.py): an "op" line per op with
+    every member, a "buf" line per buffer, a "plan" line with the scalars and a hash of the parameter
+    blob.  The arguments of plan_summary."""
+    L = lib()
+    fn = L.die_plan_dump
+    fn.restype = C.c_void_p
+    fn.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    err = _err_box()
+    p = fn(model_path.encode(), max_batch, int(side_branches), int(precision == "fp32"),
+           int(fuse_pairs) | 2 * int(fuse_stem_pool) | 4 * int(fuse_gap_fc) | 8 * int(fold_layernorm)
+           | 16 * int(ln_stats_epilogue), C.byref(err))
+    if not p:
+        _raise_if(err, "plan")
+    return _take_str(p)
+
+
 def plan_report(model_path: str, precision: str = "fp32") -> Dict[str, Any]:
     """Which nodes the HIP planner cannot lower (and why): {"supported", "unsupported": [{node, op,
     error}], "blocked", "text"}.  Runs on the CPU (no GPU needed)."""
