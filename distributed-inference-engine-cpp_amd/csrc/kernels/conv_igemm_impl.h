@@ -1207,8 +1207,8 @@ __global__ __launch_bounds__(256) void conv3x3_spatial_kernel(const ConvArgs p, 
 template <int BM, int BN, int STAGES, int BKS = BK>
 bool launch_glds(int mode, dim3 grid, hipStream_t s, const ConvArgs& b, int kt_per) {
   const bool mode0 = mode == 0;
-  if (mode == 3) {  // patchify convs (ViT patch embedding): 1- and 2-stage loops only
-    if constexpr (STAGES <= 2) {
+  if (mode == 3) {  // patchify convs (ViT patch embedding): 1-, 2- and 3-stage loops only
+    if constexpr (STAGES <= 3) {
       if (b.split) {
         if constexpr (STAGES * (BM + BN) * BKS * 4 <= 160 * 1024)
           hipLaunchKernelGGL((conv_glds_kernel<BM, BN, 3, STAGES, true, BKS>), grid, dim3(256), 0, s, b, kt_per);

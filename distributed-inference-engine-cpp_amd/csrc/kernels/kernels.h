@@ -101,6 +101,8 @@ inline size_t streamk_workspace_bytes(int P, int bm, int bn) { return static_cas
 // 1..4 = LDS-DMA ring of 2, 3, 4, 6 stages (variants 1-4: 1x1 with K % 64 == 0, or Cin % 64 == 0;
 // 6 stages only where they fit the LDS; they return hipErrorInvalidValue otherwise so a tuner can
 // skip them).  The deep rings keep more K-steps in flight for the latency-bound small-M layers.
+// A patchify conv (kernel == stride > 1, no padding, dil 1, KW * Cin % 64 == 0, Cin % 64 != 0) takes
+// the rings of 2 and 3 stages and the 1-stage loop (variants 1, 2, 5) only.
 // Variant 5 = the LDS-DMA loop with ONE stage (no ring): for K <= 64 layers, where the smaller LDS
 // footprint fits more blocks per CU.  Variant 6 = spatially tiled 3x3/s1/p1 kernel (8x8 pixels x 64
 // channels per block, input patch staged once per 64-channel slice; 64x64 tile config only).

@@ -76,11 +76,22 @@ NUM_CFGS = 40  # kernels.h TileCfg (variant 7 = the 8-wave wide tile, cfg 28 onl
 #               variant 9 = the four-tile 3x3 kernel, cfg 39 only)
 
 
+def _pads4(pad):
+    """int -> the same pad on all four sides; (top, left, bottom, right) -> itself, as ints."""
+    if isinstance(pad, (tuple, list)):
+        if len(pad) != 4:
+            raise ValueError("pad must be an int or (top, left, bottom, right), got %r" % (pad,))
+        return tuple(int(v) for v in pad)
+    return (int(pad),) * 4
+
+
 class ConvProblem:
     """One implicit-GEMM conv problem with packed weights and preallocated outputs, re-launchable with
     any (config, split-K, fused) choice -- used by conv2d_nhwc and by tools/conv_bench.py.
     x_nhwc: [B,H,W,Cin] bf16 (split: any float dtype, converted to hi/lo planes), w: [Cout,Cin,KH,KW]
-    float.  split = fp32 mode: x/res/out/out2 are split planes and the weights are packed hi + lo."""
+    float.  pad: one int for all four sides, or (top, left, bottom, right) -- the kernels offset by
+    top / left and bound-check the input, the bottom / right pads only enter Ho / Wo.
+    split = fp32 mode: x/res/out/out2 are split planes and the weights are packed hi + lo."""
 
     def __init__(self, x_nhwc, w, bias=None, stride=1, pad=0, dil=1, relu=False, res=None, out_f32=False,
                  scale2=None, shift2=None, relu2=False, max_splits=16, split=False):
@@ -90,8 +101,9 @@ class ConvProblem:
         cout, cin, kh, kw = w.shape
         self.split = split
         self.wp, K, Kpad = pack_conv_weight(w, Cs, split=split)
-        Ho = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1
-        Wo = (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
+        pt, pl, pb, pr = _pads4(pad)
+        Ho = (H + pt + pb - dil * (kh - 1) - 1) // stride + 1
+        Wo = (W + pl + pr - dil * (kw - 1) - 1) // stride + 1
         dev = x_nhwc.device
 
         def padded(v):
@@ -111,8 +123,8 @@ class ConvProblem:
                     torch.empty(np_ + (B, Ho, Wo, cout), dtype=torch.bfloat16, device=dev))
         self.out2 = (torch.empty(np_ + (B, Ho, Wo, cout), dtype=torch.bfloat16, device=dev)
                      if scale2 is not None else None)
-        self.geom = dict(B=B, H=H, W=W, Cin=Cs, Ho=Ho, Wo=Wo, N=cout, KH=kh, KW=kw, stride=stride, pad_h=pad,
-                         pad_w=pad, dil=dil, K=K, Kpad=Kpad, relu=int(relu), relu2=int(relu2))
+        self.geom = dict(B=B, H=H, W=W, Cin=Cs, Ho=Ho, Wo=Wo, N=cout, KH=kh, KW=kw, stride=stride, pad_h=pt,
+                         pad_w=pl, dil=dil, K=K, Kpad=Kpad, relu=int(relu), relu2=int(relu2))
         if split:
             self.geom.update(split=1, wplane=int(self.wp[0].numel()))
         self.zeros = torch.zeros(Kpad + 64, dtype=torch.int16, device=dev)  # zero page >= Kpad + 64
@@ -161,7 +173,7 @@ class ConvProblem:
 
 def conv2d_nhwc(x_nhwc, w, bias=None, stride=1, pad=0, dil=1, relu=False, res=None, out_f32=False,
                 scale2=None, shift2=None, relu2=False, tile=-1, splits=1, fused_splitk=True, split=False):
-    """Implicit-GEMM conv.  x_nhwc: [B,H,W,Cin] bf16, w: [Cout,Cin,KH,KW] float.
+    """Implicit-GEMM conv.  x_nhwc: [B,H,W,Cin] bf16, w: [Cout,Cin,KH,KW] float; pad as ConvProblem takes it.
     Returns (out, out2) in NHWC ([B,Ho,Wo,Cout]); out is f32 if out_f32 else bf16.
     split (fp32 mode): x/res any float dtype; outputs are the fp32 values of the split planes."""
     pr = ConvProblem(x_nhwc, w, bias, stride, pad, dil, relu, res, out_f32, scale2, shift2, relu2, max_splits=splits,

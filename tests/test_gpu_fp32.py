@@ -319,7 +319,7 @@ def test_fused_nchw_stem_kernel(native, B, H, W, relu, max_blocks, split):
 @pytest.mark.parametrize("split", [True, False])
 def test_patchify_conv_lds_dma_mode(native, split):
     """Patchify convs (stride == kernel, no padding: the ViT patch embedding) run the LDS-DMA loops
-    with each 64-wide K-step read as a contiguous piece of one input row (MODE 3), 1- and 2-stage."""
+    with each 64-wide K-step read as a contiguous piece of one input row (MODE 3), 1- to 3-stage."""
     torch = _t()
     from die_amd.ops import kernels as K
 
