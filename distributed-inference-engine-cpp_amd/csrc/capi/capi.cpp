@@ -758,4 +758,8 @@ double die_parse_bench(const char* body, long n, int iters, int simd) {
   set_json_simd(true);
   return us;
 }
+
+// The SIMD token converters of the /infer parser on (default) or off: off, every token goes through
+// the scalar SWAR converter or the strict scanner (tests run each corpus both ways).
+void die_set_json_simd(int on) { set_json_simd(on != 0); }
 }

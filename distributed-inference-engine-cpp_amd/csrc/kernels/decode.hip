@@ -240,7 +240,7 @@ __device__ bool convert_token(At s, int n, float& out) {  // s(i): byte i of the
   int i = 0;
   while (i < n && is_ws(s(i))) ++i;
   while (n > i && is_ws(s(n - 1))) --n;
-  if (i >= n) return false;
+  if (i >= n || n - i > HALO) return false;  // empty, or longer than the device converts
   const bool neg = s(i) == '-';
   i += neg;
   if (i >= n || s(i) - '0' > 9u) return false;

@@ -115,6 +115,7 @@ def lib() -> C.CDLL:
         sig("die_loadgen_run_verify", vp, cp, f32p, C.c_long, f32p, C.c_long, errp)
         sig("die_loadgen_run_cb", vp, cp, f32p, C.c_long, f32p, C.c_long, _READY_CB, errp)
         sig("die_parse_bench", C.c_double, cp, C.c_long, C.c_int, C.c_int)
+        sig("die_set_json_simd", None, C.c_int)
         i32p = C.POINTER(C.c_int)
         sig("die_dp_shard", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p)
         sig("die_dp_per", C.c_int, C.c_int, C.c_int)
@@ -169,6 +170,11 @@ def parse_infer(body: bytes, cap: int) -> Tuple[str, np.ndarray, int]:
 def parse_bench(body: bytes, iters: int = 20, simd: bool = True) -> float:
     """Average microseconds to parse `body` as an /infer request (host parser benchmark)."""
     return lib().die_parse_bench(body, len(body), iters, int(simd))
+
+
+def set_json_simd(on: bool) -> None:
+    """Process-wide switch of the parser's SIMD token converters (json.h set_json_simd); default on."""
+    lib().die_set_json_simd(int(bool(on)))
 
 
 def format_floats(v: np.ndarray) -> str:

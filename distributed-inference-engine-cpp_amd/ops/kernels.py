@@ -742,6 +742,12 @@ def attention_qkv_split(qkv, heads, scale=None, bias=None, causal=False, key_mas
 
 # ---- device JSON decode (csrc/kernels/decode.hip) ---------------------------------------------------
 
+def set_decode_variant(v):
+    """Process-wide decode variant (kernels.h set_decode_variant): 0 = packed samples on the nibble-level
+    kernels (default), 1 = packed samples expanded to characters by the character kernels (tests)."""
+    native.kernels().die_kern_set_decode_variant(int(v))
+
+
 def decode_json_numbers(texts, numel, text_cap=None, slot_order=None, packed=False):
     """Decode number-list texts (bytes, the inside of a JSON array; None = skipped sample) on the GPU.
     slot_order: optional permutation; sample i's text is then placed in arena slot slot_order[i]

@@ -7,6 +7,8 @@ import time
 import numpy as np
 import pytest
 
+import decimal_oracle
+
 
 def py_fnv1a(s: str) -> int:
     h = 2166136261
@@ -179,8 +181,8 @@ def test_parse_infer_floats_exact(native, fmt):
     body = ('{"request_id": "r-1", "input_data": [%s], "extra": {"k": [1,2]}}' % txt).encode()
     rid, out, n = native.parse_infer(body, 6000)
     assert rid == "r-1" and n == 5000
-    ref = np.array([float(s) for s in txt.split(",")], dtype=np.float64).astype(np.float32)
-    assert np.array_equal(out.view(np.uint32), ref.view(np.uint32))
+    ref = np.array([decimal_oracle.f32_bits(s) for s in txt.split(",")], dtype=np.uint32)  # exact, one rounding
+    assert np.array_equal(out.view(np.uint32), ref)
 
 
 def test_parse_infer_errors(native):
