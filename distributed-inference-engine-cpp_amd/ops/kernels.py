@@ -629,9 +629,10 @@ def pool_tokens(x, key_mask=None, clip_min=0.0, normalize=False, eps=1e-12, spli
 _LOG2E = 1.4426950408889634
 
 
-def _attention_bias(bias, S, heads):
+def _attention_bias(bias, S, heads, pad=0.0):
     """bias [S, S] or [H, S, S] fp32, natural units -> (the kernel's table [Hb][S][Sp] with Sp = S
-    rounded up to 32, pre-multiplied by log2(e) (the kernel's softmax runs in exp2), Hb, Sp)."""
+    rounded up to 32, pre-multiplied by log2(e) (the kernel's softmax runs in exp2), Hb, Sp).
+    pad: what the pad columns [S, Sp) hold (any finite value: the kernel masks those keys)."""
     import torch
 
     if bias.dim() == 2:
@@ -640,13 +641,13 @@ def _attention_bias(bias, S, heads):
         raise ValueError("attention bias must be [S, S] or [H, S, S] with S = %d, H = %d, got %s"
                          % (S, heads, tuple(bias.shape)))
     Sp = (S + 31) // 32 * 32
-    table = torch.zeros((bias.shape[0], S, Sp), dtype=torch.float32, device=bias.device)
+    table = torch.full((bias.shape[0], S, Sp), float(pad), dtype=torch.float32, device=bias.device)
     table[..., :S] = bias.float() * _LOG2E
     return table, int(bias.shape[0]), Sp
 
 
 def _attention_launch(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, split, bias, causal, what, key_mask=None,
-                      kv_heads=None):
+                      kv_heads=None, bias_pad=0.0):
     if kv_heads is not None:  # the entry point with kv_heads (grouped-query attention), whatever the masks
         kvis = kend = None
         Sp = (S + 31) // 32 * 32
@@ -656,7 +657,7 @@ def _attention_launch(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, spli
             kvis, kend = key_mask if isinstance(key_mask, (tuple, list)) else key_mask_data(key_mask)
             if tuple(kvis.shape) != (B, Sp) or tuple(kend.shape) != (B,):
                 raise ValueError("key mask must be bool [B, S] or (kvis [B, Sp] fp32, kend [B] int32), B = %d, S = %d" % (B, S))
-        table, hb, _ = _attention_bias(bias, S, heads) if bias is not None else (None, 0, 0)
+        table, hb, _ = _attention_bias(bias, S, heads, bias_pad) if bias is not None else (None, 0, 0)
         rc = native.kernels().die_kern_attention_gqa(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, _stream(), split,
                                                      _ptr(table), hb, Sp if (table is not None or kvis is not None) else 0,
                                                      int(bool(causal)), _ptr(kvis), _ptr(kend), int(kv_heads))
@@ -667,20 +668,32 @@ def _attention_launch(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, spli
         Sp = (S + 31) // 32 * 32
         if tuple(kvis.shape) != (B, Sp) or tuple(kend.shape) != (B,):
             raise ValueError("key mask must be bool [B, S] or (kvis [B, Sp] fp32, kend [B] int32), B = %d, S = %d" % (B, S))
-        table, hb, _ = _attention_bias(bias, S, heads) if bias is not None else (None, 0, 0)
+        table, hb, _ = _attention_bias(bias, S, heads, bias_pad) if bias is not None else (None, 0, 0)
         rc = native.kernels().die_kern_attention_keymask(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, _stream(),
                                                          split, _ptr(table), hb, Sp, int(bool(causal)), _ptr(kvis),
                                                          _ptr(kend))
     elif bias is None and not causal:  # the unmasked entry point, as before
         rc = native.kernels().die_kern_attention(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, _stream(), split)
     else:
-        table, hb, Sp = _attention_bias(bias, S, heads) if bias is not None else (None, 0, 0)
+        table, hb, Sp = _attention_bias(bias, S, heads, bias_pad) if bias is not None else (None, 0, 0)
         rc = native.kernels().die_kern_attention_masked(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, _stream(),
                                                         split, _ptr(table), hb, Sp, int(bool(causal)))
     _check(rc, what)
 
 
-def attention(q, k, v, heads, scale=None, bias=None, causal=False, key_mask=None, kv_heads=None):
+def attention_launch(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, scale, split=False, bias=None, causal=False,
+                     key_mask=None, kv_heads=None, bias_pad=0.0):
+    """The kernel's own calling convention, for callers that own the storage (tests of row pitches,
+    column offsets and caller-owned outputs): q, k, v, out are device addresses of the first element of
+    [B * S] rows of 16-bit elements at pitches ldq, ldk, ldv (multiples of 8) and ldo (a multiple of
+    4), q and out with heads * D columns, k and v with (kv_heads or heads) * D.  split: each is the hi
+    plane and its lo plane lies B * S * pitch elements behind it.  The masks are attention()'s;
+    bias_pad fills the table's pad columns."""
+    _attention_launch(int(q), int(k), int(v), int(out), B, S, heads, D, ldq, ldk, ldv, ldo, float(scale), int(bool(split)),
+                      bias, causal, "attention", key_mask, kv_heads, bias_pad)
+
+
+def attention(q, k, v, heads, scale=None, bias=None, causal=False, key_mask=None, kv_heads=None, out=None, bias_pad=0.0):
     """q/k/v: [B, S, H*D] bf16 (may be column slices of a wider tensor, row stride = stride(1)).
     Returns softmax(scale * Q K^T + bias) V merged back to [B, S, H*D] bf16.
     bias: fp32 [S, S] (shared by the heads) or [H, S, S], natural units, -inf = masked, the same for
@@ -691,17 +704,21 @@ def attention(q, k, v, heads, scale=None, bias=None, causal=False, key_mask=None
     without any visible key gets all-zero rows.
     kv_heads: grouped-query / multi-query attention -- k / v are [B, S, kv_heads * D] and query head h
     reads their head h // (heads // kv_heads).  Head dim 64 or 128, no bias; kv_heads = heads is the
-    multi-head launch."""
+    multi-head launch.
+    out: a [B, S, H*D] bf16 tensor to write into (like q, it may be a column slice of wider rows);
+    bias_pad: the value in the bias table's pad columns (any finite one gives the same result)."""
     import torch
 
     B, S, C = q.shape
     D = C // heads
-    for t in (q, k, v):
+    if out is None:
+        out = torch.empty((B, S, C), dtype=torch.bfloat16, device=q.device)
+    assert tuple(out.shape) == (B, S, C) and out.dtype == torch.bfloat16
+    for t in (q, k, v, out):
         assert t.stride(2) == 1 and t.stride(0) == S * t.stride(1), "rows must be [B*S][ld] with unit column stride"
-    out = torch.empty((B, S, C), dtype=torch.bfloat16, device=q.device)
     sc = float(scale if scale is not None else 1.0 / np.sqrt(D))
-    _attention_launch(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, S, heads, D, q.stride(1), k.stride(1), v.stride(1), C,
-                      sc, 0, bias, causal, "attention", key_mask, kv_heads)
+    _attention_launch(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, S, heads, D, q.stride(1), k.stride(1), v.stride(1),
+                      out.stride(1), sc, 0, bias, causal, "attention", key_mask, kv_heads, bias_pad)
     return out
 
 
@@ -711,7 +728,7 @@ def set_attention_variant(v):
     native.kernels().die_kern_set_attention_variant(int(v))
 
 
-def attention_qkv_split(qkv, heads, scale=None, bias=None, causal=False, key_mask=None, kv_heads=None):
+def attention_qkv_split(qkv, heads, scale=None, bias=None, causal=False, key_mask=None, kv_heads=None, bias_pad=0.0):
     """fp32 mode: qkv [B, S, 3*C] float (Q | K | V columns) -> fp32 [B, S, C] through the split kernel
     (planes of the packed QKV rows, like the engine's fused QKV GEMM output).  bias / causal: as
     attention() takes them (the bias is fp32 in both precisions); key_mask: likewise.
@@ -727,7 +744,7 @@ def attention_qkv_split(qkv, heads, scale=None, bias=None, causal=False, key_mas
         sc = float(scale if scale is not None else 1.0 / np.sqrt(D))
         base = _ptr(planes)
         _attention_launch(base, base + 2 * C, base + 2 * (C + Ckv), _ptr(out), B, S, heads, D, C3, C3, C3, C, sc, 1, bias,
-                          causal, "attention (split)", key_mask, kv_heads)
+                          causal, "attention (split)", key_mask, kv_heads, bias_pad)
         return join_planes(out)
     C = C3 // 3
     D = C // heads
@@ -736,7 +753,7 @@ def attention_qkv_split(qkv, heads, scale=None, bias=None, causal=False, key_mas
     sc = float(scale if scale is not None else 1.0 / np.sqrt(D))
     base = _ptr(planes)
     _attention_launch(base, base + 2 * C, base + 4 * C, _ptr(out), B, S, heads, D, C3, C3, C3, C, sc, 1, bias, causal,
-                      "attention (split)", key_mask)
+                      "attention (split)", key_mask, None, bias_pad)
     return join_planes(out)
 
 
