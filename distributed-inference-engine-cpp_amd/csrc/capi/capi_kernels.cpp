@@ -26,6 +26,28 @@ int geti(const Json& j, const char* k, int d) {
   auto* v = j.find(k);
   return v ? static_cast<int>(v->as_int()) : d;
 }
+// Reader of a launcher's geometry JSON whose keys are exactly the members of its argument struct
+// (device addresses as integers).  A key that is missing leaves the member at its default; a key
+// that no member took makes done() throw, so a misspelt key never silently becomes a default.
+class Geom {
+ public:
+  explicit Geom(const char* text) : j_(Json::parse(text)) {}
+  void operator()(const char* k, int& m) { if (auto* v = take(k)) m = static_cast<int>(v->as_int()); }
+  void operator()(const char* k, size_t& m) { if (auto* v = take(k)) m = static_cast<size_t>(v->as_int()); }
+  void operator()(const char* k, float& m) { if (auto* v = take(k)) m = static_cast<float>(v->as_double()); }
+  template <typename T>
+  void operator()(const char* k, T*& m) { if (auto* v = take(k)) m = P<T>(static_cast<uint64_t>(v->as_int())); }
+  void done() const { if (taken_ != j_.as_object().size()) throw JsonError("unknown key in geometry"); }
+
+ private:
+  const Json* take(const char* k) {
+    const Json* v = j_.find(k);
+    taken_ += v != nullptr;
+    return v;
+  }
+  Json j_;
+  size_t taken_ = 0;
+};
 char* dup(const std::string& s) {
   char* p = static_cast<char*>(std::malloc(s.size() + 1));
   std::memcpy(p, s.data(), s.size() + 1);
@@ -226,31 +248,18 @@ int die_kern_input_prep(uint64_t x, uint64_t scale, uint64_t shift, uint64_t out
                                            P<uint16_t>(out), B, C, H, W, Cp, S(stream), split));
 }
 
-int die_kern_pool2d(uint64_t x, uint64_t y, int B, int H, int W, int C, int Ho, int Wo, int kh, int kw, int sh, int sw,
-                    int ph, int pw, int is_max, int cip, uint64_t stream, int split) {
-  return static_cast<int>(kern::pool2d(P<const uint16_t>(x), P<uint16_t>(y), B, H, W, C, Ho, Wo, kh, kw, sh, sw, ph,
-                                       pw, is_max, cip, S(stream), nullptr, nullptr, nullptr, 0, split));
-}
-
-int die_kern_gap(uint64_t x, uint64_t out, uint64_t out_f32, uint64_t scale, uint64_t shift, int relu, int B, int HW,
-                 int C, uint64_t stream, int split) {
-  return static_cast<int>(kern::global_avgpool(P<const uint16_t>(x), P<uint16_t>(out), P<float>(out_f32),
-                                               P<const float>(scale), P<const float>(shift), relu, B, HW, C, S(stream),
-                                               nullptr, split));
-}
-
-// die_kern_pool2d plus the live batch, the fused per-channel affine on the pooled value and act (0 = none)
-int die_kern_pool2d_ex(uint64_t x, uint64_t y, int B, int H, int W, int C, int Ho, int Wo, int kh, int kw, int sh,
-                       int sw, int ph, int pw, int is_max, int cip, uint64_t stream, int split, uint64_t live,
-                       uint64_t scale, uint64_t shift, int act) {
+// live 0 = the whole batch; scale / shift (0 = none): per-channel affine on the pooled value, then act (0 = none)
+int die_kern_pool2d(uint64_t x, uint64_t y, int B, int H, int W, int C, int Ho, int Wo, int kh, int kw, int sh,
+                    int sw, int ph, int pw, int is_max, int cip, uint64_t stream, int split, uint64_t live,
+                    uint64_t scale, uint64_t shift, int act) {
   return static_cast<int>(kern::pool2d(P<const uint16_t>(x), P<uint16_t>(y), B, H, W, C, Ho, Wo, kh, kw, sh, sw, ph,
                                        pw, is_max, cip, S(stream), P<const long long>(live), P<const float>(scale),
                                        P<const float>(shift), act, split));
 }
 
-// die_kern_gap plus the live batch and the reduction mode (0 mean, 1 sum, 2 max)
-int die_kern_gap_ex(uint64_t x, uint64_t out, uint64_t out_f32, uint64_t scale, uint64_t shift, int relu, int B, int HW,
-                    int C, uint64_t stream, int split, uint64_t live, int mode) {
+// live 0 = the whole batch; mode 0 mean, 1 sum, 2 max
+int die_kern_gap(uint64_t x, uint64_t out, uint64_t out_f32, uint64_t scale, uint64_t shift, int relu, int B, int HW,
+                 int C, uint64_t stream, int split, uint64_t live, int mode) {
   return static_cast<int>(kern::global_avgpool(P<const uint16_t>(x), P<uint16_t>(out), P<float>(out_f32),
                                                P<const float>(scale), P<const float>(shift), relu, B, HW, C, S(stream),
                                                P<const long long>(live), split, mode));
@@ -333,15 +342,9 @@ int die_kern_nhwc_to_nchw(uint64_t x, uint64_t y, int B, int H, int W, int C, ui
   return static_cast<int>(kern::nhwc_to_nchw_f32(P<const uint16_t>(x), P<float>(y), B, H, W, C, S(stream), split));
 }
 
+// kernels.h layernorm_rows: Cl logical columns (0 = C), stats 0 = none, rms != 0 = RMSNorm (beta unused)
 int die_kern_layernorm(uint64_t x, uint64_t y, uint64_t gamma, uint64_t beta, float eps, long long rows, int C,
-                       uint64_t stream, int split, int variant) {
-  return static_cast<int>(kern::layernorm_rows(P<const uint16_t>(x), P<uint16_t>(y), P<const float>(gamma),
-                                               P<const float>(beta), eps, rows, C, S(stream), split, 0, variant));
-}
-
-// layernorm_rows with every argument: Cl logical columns (0 = C), stats 0 = none, rms != 0 = RMSNorm (beta unused)
-int die_kern_layernorm_ex(uint64_t x, uint64_t y, uint64_t gamma, uint64_t beta, float eps, long long rows, int C,
-                          uint64_t stream, int split, int Cl, int variant, uint64_t stats, int rms) {
+                       uint64_t stream, int split, int Cl, int variant, uint64_t stats, int rms) {
   return static_cast<int>(kern::layernorm_rows(P<const uint16_t>(x), P<uint16_t>(y), P<const float>(gamma),
                                                P<const float>(beta), eps, rows, C, S(stream), split, Cl, variant,
                                                P<float>(stats), rms));
@@ -380,75 +383,65 @@ void die_kern_set_decode_variant(int v) { kern::set_decode_variant(v); }
 void die_kern_set_layernorm_xcd(int v) { kern::set_layernorm_xcd(v); }
 void die_kern_set_pair_shared_w(int v) { kern::set_pair_shared_w(v); }
 
-int die_kern_attention(uint64_t q, uint64_t k, uint64_t v, uint64_t out, int B, int Sq, int H, int D, int ldq, int ldk,
-                       int ldv, int ldo, float scale, uint64_t stream, int split) {
-  return static_cast<int>(kern::attention(P<const uint16_t>(q), P<const uint16_t>(k), P<const uint16_t>(v),
-                                          P<uint16_t>(out), B, Sq, H, D, ldq, ldk, ldv, ldo, scale, S(stream), split));
+// The token-model launchers take a geometry JSON whose keys are exactly the members of their argument
+// struct (kernels.h; device addresses as integers, a missing key = the member's default) and the
+// stream.  An unknown key returns -1 and launches nothing.  Floats (scale, pad_c, clip_min, eps)
+// arrive bit-exact: the caller prints the double with all its digits (Python's repr), Json parses
+// it back to that double (from_chars / strtod) and it is cast to float once, here -- the same single
+// rounding a c_float argument gets.
+int die_kern_attention(const char* geom, uint64_t stream) {
+  try {
+    Geom g(geom);
+    kern::AttentionArgs a;
+    g("q", a.q), g("k", a.k), g("v", a.v), g("out", a.out);
+    g("B", a.B), g("S", a.S), g("H", a.H), g("D", a.D);
+    g("ldq", a.ldq), g("ldk", a.ldk), g("ldv", a.ldv), g("ldo", a.ldo);
+    g("scale", a.scale), g("split", a.split);
+    g("bias", a.bias), g("bias_heads", a.bias_heads), g("Sp", a.Sp), g("causal", a.causal);
+    g("kvis", a.kvis), g("kend", a.kend), g("kv_heads", a.kv_heads);
+    g.done();
+    return static_cast<int>(kern::attention(a, S(stream)));
+  } catch (...) {
+    return -1;
+  }
 }
 
-// Embedding lookup + key data (kernels.h embed_tokens); kvis / kend 0 = no key data
-int die_kern_embed_tokens(uint64_t ids, uint64_t table, int ldt, uint64_t pos, uint64_t type, uint64_t out, int B, int Sq,
-                          int V, int C, uint64_t stream, int split, uint64_t kvis, uint64_t kend, int Sp, int pad_op,
-                          float pad_c, int pad_neg, int pad_trunc) {
-  return static_cast<int>(kern::embed_tokens(P<const float>(ids), P<const float>(table), ldt, P<const float>(pos),
-                                             P<const float>(type), P<uint16_t>(out), B, Sq, V, C, S(stream), split,
-                                             P<float>(kvis), P<int>(kend), Sp, pad_op, pad_c, pad_neg, pad_trunc));
+int die_kern_embed_tokens(const char* geom, uint64_t stream) {
+  try {
+    Geom g(geom);
+    kern::EmbedArgs a;
+    g("ids", a.ids), g("types", a.types), g("mask", a.mask), g("ld_in", a.ld_in);
+    g("table", a.table), g("ldt", a.ldt), g("pos", a.pos), g("ttab", a.ttab), g("ldtt", a.ldtt), g("T", a.T);
+    g("out", a.out), g("B", a.B), g("S", a.S), g("V", a.V), g("C", a.C), g("split", a.split);
+    g("kvis", a.kvis), g("kend", a.kend), g("Sp", a.Sp);
+    g("pad_op", a.pad_op), g("pad_c", a.pad_c), g("pad_neg", a.pad_neg), g("pad_trunc", a.pad_trunc);
+    g.done();
+    return static_cast<int>(kern::embed_tokens(a, S(stream)));
+  } catch (...) {
+    return -1;
+  }
 }
 
-// The same over packed request rows of ld_in floats with a type-id and a mask segment (kernels.h
-// embed_inputs); types / mask 0 = none, ttab = the type table (types set) or the one type row
-int die_kern_embed_inputs(uint64_t ids, uint64_t types, uint64_t mask, int ld_in, uint64_t table, int ldt, uint64_t pos,
-                          uint64_t ttab, int ldtt, int T, uint64_t out, int B, int Sq, int V, int C, uint64_t stream,
-                          int split, uint64_t kvis, uint64_t kend, int Sp, int pad_op, float pad_c, int pad_neg,
-                          int pad_trunc) {
-  return static_cast<int>(kern::embed_inputs(P<const float>(ids), P<const float>(types), P<const float>(mask), ld_in,
-                                             P<const float>(table), ldt, P<const float>(pos), P<const float>(ttab), ldtt,
-                                             T, P<uint16_t>(out), B, Sq, V, C, S(stream), split, P<float>(kvis),
-                                             P<int>(kend), Sp, pad_op, pad_c, pad_neg, pad_trunc));
-}
-
-// Token pooling + L2 normalisation (kernels.h pool_tokens); kvis / kend 0 = unmasked, ws / counters 0 = none
-int die_kern_pool_tokens(uint64_t x, uint64_t out, uint64_t out_f32, int B, int Sq, int C, int D, uint64_t kvis,
-                         uint64_t kend, int Sp, float clip_min, int normalize, float eps, uint64_t stream, uint64_t live,
-                         int split, uint64_t ws, uint64_t ws_bytes, uint64_t counters, int counters_n) {
-  return static_cast<int>(kern::pool_tokens(P<const uint16_t>(x), P<uint16_t>(out), P<float>(out_f32), B, Sq, C, D,
-                                            P<const float>(kvis), P<const int>(kend), Sp, clip_min, normalize, eps,
-                                            S(stream), P<const long long>(live), split, P<float>(ws),
-                                            static_cast<size_t>(ws_bytes), P<int>(counters), counters_n));
+int die_kern_pool_tokens(const char* geom, uint64_t stream) {
+  try {
+    Geom g(geom);
+    kern::PoolTokensArgs a;
+    g("x", a.x), g("out", a.out), g("out_f32", a.out_f32);
+    g("B", a.B), g("S", a.S), g("C", a.C), g("D", a.D);
+    g("kvis", a.kvis), g("kend", a.kend), g("Sp", a.Sp);
+    g("clip_min", a.clip_min), g("normalize", a.normalize), g("eps", a.eps);
+    g("live", a.live), g("split", a.split);
+    g("ws", a.ws), g("ws_bytes", a.ws_bytes), g("counters", a.counters), g("counters_n", a.counters_n);
+    g.done();
+    return static_cast<int>(kern::pool_tokens(a, S(stream)));
+  } catch (...) {
+    return -1;
+  }
 }
 uint64_t die_kern_pool_tokens_ws_bytes(int B, int C) { return kern::pool_tokens_ws_bytes(B, C); }
 
 // the kernels' id -> table row rule on the host (k::token_index)
 int die_token_index(float x, int V) { return kern::token_index_host(x, V); }
-
-// die_kern_attention_masked plus the per-sample key mask (kvis [B][Sp] fp32, kend [B] int; 0 = none)
-int die_kern_attention_keymask(uint64_t q, uint64_t k, uint64_t v, uint64_t out, int B, int Sq, int H, int D, int ldq,
-                               int ldk, int ldv, int ldo, float scale, uint64_t stream, int split, uint64_t bias,
-                               int bias_heads, int Sp, int causal, uint64_t kvis, uint64_t kend) {
-  return static_cast<int>(kern::attention(P<const uint16_t>(q), P<const uint16_t>(k), P<const uint16_t>(v),
-                                          P<uint16_t>(out), B, Sq, H, D, ldq, ldk, ldv, ldo, scale, S(stream), split,
-                                          P<const float>(bias), bias_heads, Sp, causal, P<const float>(kvis),
-                                          P<const int>(kend)));
-}
-
-// die_kern_attention_keymask plus kv_heads: k / v hold kv_heads heads (0 or H: the same launch as without)
-int die_kern_attention_gqa(uint64_t q, uint64_t k, uint64_t v, uint64_t out, int B, int Sq, int H, int D, int ldq,
-                           int ldk, int ldv, int ldo, float scale, uint64_t stream, int split, uint64_t bias,
-                           int bias_heads, int Sp, int causal, uint64_t kvis, uint64_t kend, int kv_heads) {
-  return static_cast<int>(kern::attention(P<const uint16_t>(q), P<const uint16_t>(k), P<const uint16_t>(v),
-                                          P<uint16_t>(out), B, Sq, H, D, ldq, ldk, ldv, ldo, scale, S(stream), split,
-                                          P<const float>(bias), bias_heads, Sp, causal, P<const float>(kvis),
-                                          P<const int>(kend), kv_heads));
-}
-
-// bias: fp32 [bias_heads][Sq][Sp] pre-multiplied by log2(e) (kernels.h attention), 0 = none
-int die_kern_attention_masked(uint64_t q, uint64_t k, uint64_t v, uint64_t out, int B, int Sq, int H, int D, int ldq,
-                              int ldk, int ldv, int ldo, float scale, uint64_t stream, int split, uint64_t bias,
-                              int bias_heads, int Sp, int causal) {
-  return static_cast<int>(kern::attention(P<const uint16_t>(q), P<const uint16_t>(k), P<const uint16_t>(v),
-                                          P<uint16_t>(out), B, Sq, H, D, ldq, ldk, ldv, ldo, scale, S(stream), split,
-                                          P<const float>(bias), bias_heads, Sp, causal));
-}
 
 // geometry JSON: B,H,W,Cin,Ho,Wo,Cout,groups,KH,KW,stride,pad_h,pad_w,dil,act,clip_lo,clip_hi,split
 static kern::GConvArgs gconv_geometry(const char* geom) {
@@ -516,18 +509,10 @@ long long die_decode_scratch_bytes(int max_batch, long long text_cap) {
   return static_cast<long long>(kern::decode_scratch_bytes(max_batch, static_cast<size_t>(text_cap)));
 }
 
-int die_kern_decode(uint64_t text, uint64_t offs, long long text_cap, uint64_t lens, int B, uint64_t out,
-                    long long numel, uint64_t status, uint64_t ntok, uint64_t scratch, uint64_t stream) {
-  return static_cast<int>(kern::decode_json_numbers(P<const unsigned char>(text), P<const long long>(offs),
-                                                    static_cast<size_t>(text_cap), P<const long long>(lens), B,
-                                                    P<float>(out), numel, P<int>(status), P<int>(ntok), P<void>(scratch),
-                                                    S(stream)));
-}
-
-// packed: 4-bit packed samples at packed + poffs[b] (poffs[b] < 0: raw text at text + offs[b])
-int die_kern_decode_packed(uint64_t text, uint64_t offs, uint64_t packed, uint64_t poffs, long long text_cap,
-                           uint64_t lens, int B, uint64_t out, long long numel, uint64_t status, uint64_t ntok,
-                           uint64_t scratch, uint64_t stream) {
+// packed / poffs (0 = raw text only): 4-bit packed samples at packed + poffs[b] (poffs[b] < 0: raw text at text + offs[b])
+int die_kern_decode(uint64_t text, uint64_t offs, uint64_t packed, uint64_t poffs, long long text_cap,
+                    uint64_t lens, int B, uint64_t out, long long numel, uint64_t status, uint64_t ntok,
+                    uint64_t scratch, uint64_t stream) {
   return static_cast<int>(kern::decode_json_numbers(P<const unsigned char>(text), P<const long long>(offs),
                                                     static_cast<size_t>(text_cap), P<const long long>(lens), B,
                                                     P<float>(out), numel, P<int>(status), P<int>(ntok), P<void>(scratch),

@@ -245,38 +245,91 @@ hipError_t HipEngine::launch_op(const PlanOp& op, size_t op_index, int B, int s,
     case PlanOp::GATHER_ROWS:
       e = kern::gather_rows(cbf(op.in), bf(op.out), B, op.S, op.gidx, op.C, st, sp_);
       break;
-    case PlanOp::ATTENTION:
-      e = kern::attention(cbf(op.in) + op.col[0], cbf(op.in2) + op.col[1], cbf(op.in3) + op.col[2], bf(op.out), B, op.S,
-                          op.nh, op.hd, op.ld[0], op.ld[1], op.ld[2], op.C, op.fscale, st, sp_,
-                          op.bias_heads ? prm(op.bias_off) : nullptr, op.bias_heads,
-                          op.bias_heads || op.key_mask ? kern::key_pitch(op.S) : 0, op.causal,
-                          op.key_mask ? cf32(op.in4) : nullptr,
-                          op.key_mask ? static_cast<const int*>(buf(op.in5)) : nullptr, op.kv_heads);
+    case PlanOp::ATTENTION: {
+      kern::AttentionArgs a;
+      a.q = cbf(op.in) + op.col[0];
+      a.k = cbf(op.in2) + op.col[1];
+      a.v = cbf(op.in3) + op.col[2];
+      a.out = bf(op.out);
+      a.B = B;
+      a.S = op.S;
+      a.H = op.nh;
+      a.D = op.hd;
+      a.ldq = op.ld[0];
+      a.ldk = op.ld[1];
+      a.ldv = op.ld[2];
+      a.ldo = op.C;
+      a.scale = op.fscale;
+      a.split = sp_;
+      a.bias = op.bias_heads ? prm(op.bias_off) : nullptr;
+      a.bias_heads = op.bias_heads;
+      a.Sp = op.bias_heads || op.key_mask ? kern::key_pitch(op.S) : 0;
+      a.causal = op.causal;
+      a.kvis = op.key_mask ? cf32(op.in4) : nullptr;
+      a.kend = op.key_mask ? static_cast<const int*>(buf(op.in5)) : nullptr;
+      a.kv_heads = op.kv_heads;
+      e = kern::attention(a, st);
       break;
-    case PlanOp::EMBED_TOKENS:
+    }
+    case PlanOp::EMBED_TOKENS: {
+      kern::EmbedArgs a;
+      a.ids = cf32(op.in);
+      a.ttab = prm(op.bias_off);
       if (op.in_ld > 0) {  // several graph inputs: segments of the packed request rows
         const float* row = cf32(op.in);
-        const bool typed = op.seg_types >= 0;
-        e = kern::embed_inputs(row + op.seg_ids, typed ? row + op.seg_types : nullptr,
-                               op.pad.src >= 0 && op.out2 >= 0 ? row + op.pad.src : nullptr, op.in_ld, prm(op.w_off),
-                               op.C, prm(op.shift_off), typed ? prm(op.type_off) : prm(op.bias_off), op.C,
-                               op.type_rows, bf(op.out), B, op.S, op.gidx, op.C, st, sp_, f32(op.out2),
-                               static_cast<int*>(buf(op.out3)), op.out2 >= 0 ? kern::key_pitch(op.S) : 0, op.pad.op,
-                               op.pad.value, op.pad.negated, op.pad.truncated);
-        break;
+        a.ids = row + op.seg_ids;
+        a.mask = op.pad.src >= 0 && op.out2 >= 0 ? row + op.pad.src : nullptr;
+        a.ld_in = op.in_ld;
+        if (op.seg_types >= 0) {
+          a.types = row + op.seg_types;
+          a.ttab = prm(op.type_off);
+        }
+        a.ldtt = op.C;
+        a.T = op.type_rows;
       }
-      e = kern::embed_tokens(cf32(op.in), prm(op.w_off), op.C, prm(op.shift_off), prm(op.bias_off), bf(op.out), B, op.S,
-                             op.gidx, op.C, st, sp_, f32(op.out2), static_cast<int*>(buf(op.out3)),
-                             op.out2 >= 0 ? kern::key_pitch(op.S) : 0, op.pad.op, op.pad.value, op.pad.negated,
-                             op.pad.truncated);
+      a.table = prm(op.w_off);
+      a.ldt = op.C;
+      a.pos = prm(op.shift_off);
+      a.out = bf(op.out);
+      a.B = B;
+      a.S = op.S;
+      a.V = op.gidx;
+      a.C = op.C;
+      a.split = sp_;
+      a.kvis = f32(op.out2);
+      a.kend = static_cast<int*>(buf(op.out3));
+      a.Sp = op.out2 >= 0 ? kern::key_pitch(op.S) : 0;
+      a.pad_op = op.pad.op;
+      a.pad_c = op.pad.value;
+      a.pad_neg = op.pad.negated;
+      a.pad_trunc = op.pad.truncated;
+      e = kern::embed_tokens(a, st);
       break;
-    case PlanOp::POOL_TOKENS:
-      e = kern::pool_tokens(cbf(op.in), op.out >= 0 ? bf(op.out) : nullptr, op.out_f32 != -1 ? f32(op.out_f32) : nullptr,
-                            B, op.S, op.C, op.Cp, op.key_mask ? cf32(op.in4) : nullptr,
-                            op.key_mask ? static_cast<const int*>(buf(op.in5)) : nullptr,
-                            op.key_mask ? kern::key_pitch(op.S) : 0, op.count_min, op.normalize, op.eps, st, live, sp_,
-                            ws, ws_bytes_, counters, kCounters);
+    }
+    case PlanOp::POOL_TOKENS: {
+      kern::PoolTokensArgs a;
+      a.x = cbf(op.in);
+      a.out = op.out >= 0 ? bf(op.out) : nullptr;
+      a.out_f32 = op.out_f32 != -1 ? f32(op.out_f32) : nullptr;
+      a.B = B;
+      a.S = op.S;
+      a.C = op.C;
+      a.D = op.Cp;
+      a.kvis = op.key_mask ? cf32(op.in4) : nullptr;
+      a.kend = op.key_mask ? static_cast<const int*>(buf(op.in5)) : nullptr;
+      a.Sp = op.key_mask ? kern::key_pitch(op.S) : 0;
+      a.clip_min = op.count_min;
+      a.normalize = op.normalize;
+      a.eps = op.eps;
+      a.live = live;
+      a.split = sp_;
+      a.ws = ws;
+      a.ws_bytes = ws_bytes_;
+      a.counters = counters;
+      a.counters_n = kCounters;
+      e = kern::pool_tokens(a, st);
       break;
+    }
     case PlanOp::ROPE:
       e = kern::rope_rows(cbf(op.in) + op.col[0], bf(op.out), prm(op.scale_off), prm(op.shift_off), B, op.S, op.nh,
                           op.hd, op.ld[0], op.C, st, sp_);

@@ -72,7 +72,7 @@ struct PlanOp {
                   // with w_off = table [gidx = V][C] f32, shift_off = pos [S][C], bias_off = type [C] (C = stored
                   // width, Cp = the model's); key data for key-masked attention when out2 >= 0: out2 = kvis
                   // f32 [kern::key_pitch(S)], out3 = kend (one int), from the pad test `pad`.
-                  // Several graph inputs (in_ld > 0, kern::embed_inputs): a sample's request row has in_ld
+                  // Several graph inputs (in_ld > 0, kern::EmbedArgs::ld_in): a sample's request row has in_ld
                   // floats, the ids at seg_ids, the type ids at seg_types (>= 0: type_off = their table
                   // [type_rows][C] f32, instead of the constant row bias_off), the mask at pad.src
     POOL_TOKENS,  // rows in [S][C] (Cp logical columns) -> one vector: out [C] (bf16 / split) or out_f32 [Cp] (the

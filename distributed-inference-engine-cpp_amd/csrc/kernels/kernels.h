@@ -388,76 +388,121 @@ hipError_t gather_rows(const uint16_t* x, uint16_t* y, int B, int S, int idx, in
 // Multi-head attention: out[b,s,h*D:(h+1)*D] = softmax(scale * Q_h K_h^T) V_h with Q/K/V rows
 // [B*S][ld*] (head h at columns h*D).  D and S as attention_supported() takes them (split: q/k/v/out
 // planes are B*S*ld of their pitch).
-// Masked: softmax(scale * Q K^T + bias) with
-//  * bias (nullable): fp32 in both precisions, [bias_heads][S][Sp] with bias_heads = 1 (shared by
-//    all heads) or H and Sp = S rounded up to a multiple of 32 (pad columns: any finite value),
-//    16-byte aligned, the same for every image of the batch.  Units: PRE-MULTIPLIED by log2(e) --
-//    the kernel's softmax runs in exp2 and adds the table to score * scale * log2(e) as it is;
-//    -inf = masked;
-//  * causal != 0: key j is visible to query i iff j <= i (from indices; combines with a bias).
-//  * kvis / kend (both or neither): the per-sample key mask embed_tokens() writes -- kvis [B][Sp]
-//    fp32, 0 = visible, -inf = padding (columns >= S: -inf), 16-byte aligned; kend [B] = 1 + the last
-//    visible key.  A block walks only the key tiles below kend[b].  Combines with a bias, not with
-//    causal.  A sample with kend = 0 gets all-zero rows (ONNX: NaN).
-// A query row with no visible key at all is otherwise undefined (ONNX gives NaN): callers reject
-// such constant masks.
-// Wrong bias_heads / Sp / alignment, a key mask together with causal, or a mask on a build without
-// the streaming kernel: hipErrorInvalidValue, nothing launched.
-// kv_heads (grouped-query / multi-query attention): k and v hold kv_heads heads (kv_heads * D
-// columns at their pitch) and query head h reads stored head h / (H / kv_heads).  0 or H: every head
-// its own K/V, the launch above bit for bit.  Otherwise the streaming kernel's GQA mode: D = 64 or
-// 128, unmasked, causal or key-masked.  A bias table, another head dim, H % kv_heads != 0, pitches
-// below kv_heads * D or q / k / v not 16-byte aligned (a column offset that is no multiple of 8):
-// hipErrorInvalidValue, nothing launched.
-hipError_t attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, int B, int S, int H,
-                     int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t s, int split = 0,
-                     const float* bias = nullptr, int bias_heads = 0, int Sp = 0, int causal = 0,
-                     const float* kvis = nullptr, const int* kend = nullptr, int kv_heads = 0);
+struct AttentionArgs {
+  const uint16_t* q = nullptr;
+  const uint16_t* k = nullptr;
+  const uint16_t* v = nullptr;
+  uint16_t* out = nullptr;
+  int B = 1, S = 1, H = 1, D = 64;
+  int ldq = 0, ldk = 0, ldv = 0, ldo = 0;  // row pitches of q / k / v / out
+  float scale = 1.f;
+  int split = 0;
+  // Masked: softmax(scale * Q K^T + bias) with
+  //  * bias (nullable): fp32 in both precisions, [bias_heads][S][Sp] with bias_heads = 1 (shared by
+  //    all heads) or H and Sp = S rounded up to a multiple of 32 (pad columns: any finite value),
+  //    16-byte aligned, the same for every image of the batch.  Units: PRE-MULTIPLIED by log2(e) --
+  //    the kernel's softmax runs in exp2 and adds the table to score * scale * log2(e) as it is;
+  //    -inf = masked;
+  //  * causal != 0: key j is visible to query i iff j <= i (from indices; combines with a bias).
+  //  * kvis / kend (both or neither): the per-sample key mask embed_tokens() writes -- kvis [B][Sp]
+  //    fp32, 0 = visible, -inf = padding (columns >= S: -inf), 16-byte aligned; kend [B] = 1 + the last
+  //    visible key.  A block walks only the key tiles below kend[b].  Combines with a bias, not with
+  //    causal.  A sample with kend = 0 gets all-zero rows (ONNX: NaN).
+  // A query row with no visible key at all is otherwise undefined (ONNX gives NaN): callers reject
+  // such constant masks.
+  // Wrong bias_heads / Sp / alignment, a key mask together with causal, or a mask on a build without
+  // the streaming kernel: hipErrorInvalidValue, nothing launched.
+  const float* bias = nullptr;
+  int bias_heads = 0;
+  int Sp = 0;
+  int causal = 0;
+  const float* kvis = nullptr;
+  const int* kend = nullptr;
+  // kv_heads (grouped-query / multi-query attention): k and v hold kv_heads heads (kv_heads * D
+  // columns at their pitch) and query head h reads stored head h / (H / kv_heads).  0 or H: every head
+  // its own K/V, the launch without it bit for bit.  Otherwise the streaming kernel's GQA mode: D = 64
+  // or 128, unmasked, causal or key-masked.  A bias table, another head dim, H % kv_heads != 0, pitches
+  // below kv_heads * D or q / k / v not 16-byte aligned (a column offset that is no multiple of 8):
+  // hipErrorInvalidValue, nothing launched.
+  int kv_heads = 0;
+};
+hipError_t attention(const AttentionArgs& a, hipStream_t s);
 // Row pitch Sp of the bias table and of the key data kvis for sequences of S keys: S rounded up to 32.
 inline int key_pitch(int S) { return (S + 31) / 32 * 32; }
 // Embedding lookup on fp32 token ids [B][S]: out[b, s, :] = table[idx(ids[b, s])] + pos[s] + type,
 // summed in fp32, stored as bf16 rows [B*S][C] (split: hi / lo planes).  idx = k::token_index
 // (common.h): truncate, clamp to [0, V - 1], NaN -> 0 -- never out of bounds, whatever the input
-// holds.  table: [V] rows of pitch ldt >= C (ldt % 4 == 0), pos (nullable) [S][C], type (nullable)
-// [C]; C % 8 == 0 is the stored width, whose pad columns hold 0 in all three; all 16-byte aligned.
-// kvis / kend (both or neither): the key data of attention()'s key mask, from the pad test
-// visible = ((trunc ? trunc(id) : id) OP pad_c) != pad_neg, OP = 0 Equal, 1 Greater, 2 Less;
-// Sp = S rounded up to 32.  One launch.
-hipError_t embed_tokens(const float* ids, const float* table, int ldt, const float* pos, const float* type,
-                        uint16_t* out, int B, int S, int V, int C, hipStream_t s, int split = 0, float* kvis = nullptr,
-                        int* kend = nullptr, int Sp = 0, int pad_op = 0, float pad_c = 0.f, int pad_neg = 1,
-                        int pad_trunc = 0);
-// embed_tokens() for requests that carry further [S] inputs next to the ids (attention_mask,
-// token_type_ids): every sample is one packed row of ld_in >= S floats, and ids / types / mask point
-// at their segment of sample 0, so element (b, s) of each is read at [b * ld_in + s].
-//   out[b, s, :] = table[idx(ids, V)] + pos[s] + ttab[idx(types, T)]      (fp32, in that order)
-//  * types (nullable): ids into ttab, [T] rows of pitch ldtt >= C (ldtt % 4 == 0), through the same
-//    k::token_index -- a bad type id clamps, never reads outside the table.  types == nullptr: ttab is
-//    embed_tokens()' one type row [C] (nullable), T / ldtt unused.
-//  * mask (nullable, needs kvis / kend): the pad test of the key data runs on the mask values
-//    instead of the ids.
-// Everything else as embed_tokens().  ld_in < S, types with T <= 0 or without / with a misaligned
-// ttab, kvis without kend: hipErrorInvalidValue, nothing launched.  One launch.
-hipError_t embed_inputs(const float* ids, const float* types, const float* mask, int ld_in, const float* table, int ldt,
-                        const float* pos, const float* ttab, int ldtt, int T, uint16_t* out, int B, int S, int V, int C,
-                        hipStream_t s, int split = 0, float* kvis = nullptr, int* kend = nullptr, int Sp = 0,
-                        int pad_op = 0, float pad_c = 0.f, int pad_neg = 1, int pad_trunc = 0);
+// holds.  One launch.
+struct EmbedArgs {
+  const float* ids = nullptr;  // [B][S], or a segment of the packed request rows (ld_in > 0)
+  // Requests that carry further [S] inputs next to the ids (attention_mask, token_type_ids): every
+  // sample is one packed row of ld_in >= S floats, and ids / types / mask point at their segment of
+  // sample 0, so element (b, s) of each is read at [b * ld_in + s].
+  //   out[b, s, :] = table[idx(ids, V)] + pos[s] + ttab[idx(types, T)]      (fp32, in that order)
+  //  * types (nullable): ids into ttab, [T] rows of pitch ldtt >= C (ldtt % 4 == 0), through the same
+  //    k::token_index -- a bad type id clamps, never reads outside the table.  types == nullptr: ttab
+  //    is the one type row [C] (nullable), T / ldtt unused.
+  //  * mask (nullable, needs kvis / kend): the pad test of the key data runs on the mask values
+  //    instead of the ids.
+  // ld_in == 0 (then no types, no mask): dense ids, the single-input kernel -- the same rows.
+  // ld_in < S otherwise, types with T <= 0 or without / with a misaligned ttab, kvis without kend:
+  // hipErrorInvalidValue, nothing launched.
+  const float* types = nullptr;
+  const float* mask = nullptr;
+  int ld_in = 0;
+  // table: [V] rows of pitch ldt >= C (ldt % 4 == 0), pos (nullable) [S][C], ttab (types == nullptr:
+  // nullable, [C]); C % 8 == 0 is the stored width, whose pad columns hold 0 in all three; all 16-byte
+  // aligned.
+  const float* table = nullptr;
+  int ldt = 0;
+  const float* pos = nullptr;
+  const float* ttab = nullptr;
+  int ldtt = 0, T = 0;
+  uint16_t* out = nullptr;
+  int B = 1, S = 1, V = 1, C = 8;
+  int split = 0;
+  // kvis / kend (both or neither): the key data of attention()'s key mask, from the pad test
+  // visible = ((trunc ? trunc(id) : id) OP pad_c) != pad_neg, OP = 0 Equal, 1 Greater, 2 Less;
+  // Sp = S rounded up to 32.
+  float* kvis = nullptr;
+  int* kend = nullptr;
+  int Sp = 0;
+  int pad_op = 0;
+  float pad_c = 0.f;
+  int pad_neg = 1, pad_trunc = 0;
+};
+hipError_t embed_tokens(const EmbedArgs& a, hipStream_t s);
 // Token pooling + L2 normalisation of bf16 / split rows x [B][S][C] (C % 8 == 0 stored, D <= C logical
-// columns) -> one vector per sample: out (nullable) bf16 / split [B][C] with the pad columns 0,
-// out_f32 (nullable) [B][D].
-//  * kvis / kend (both or neither; embed_tokens' key data, Sp = S rounded up to 32): the mean runs
-//    over the visible tokens only, sum / max(count, clip_min); a sample with none gets zeros (ONNX:
-//    NaN).  Without them: the mean of all S rows.
-//  * normalize != 0: then v / max(||v||_2, eps) over the D columns (0 where that is 0 / 0).  With
-//    S = 1 this is a row normalisation alone.
-// One launch, capturable.  normalize with C > 64 hands the row over between its column blocks:
-// ws >= pool_tokens_ws_bytes(B, C) bytes and B counters holding 0 (left at 0), neither shared with a
-// launch that may run at the same time.  Anything else: hipErrorInvalidValue, nothing launched.
+// columns) -> one vector per sample.  One launch, capturable.  Anything outside what the members
+// allow: hipErrorInvalidValue, nothing launched.
 size_t pool_tokens_ws_bytes(int B, int C);
-hipError_t pool_tokens(const uint16_t* x, uint16_t* out, float* out_f32, int B, int S, int C, int D, const float* kvis,
-                       const int* kend, int Sp, float clip_min, int normalize, float eps, hipStream_t s,
-                       const long long* live = nullptr, int split = 0, float* ws = nullptr, size_t ws_bytes = 0,
-                       int* counters = nullptr, int counters_n = 0);
+struct PoolTokensArgs {
+  const uint16_t* x = nullptr;
+  uint16_t* out = nullptr;   // nullable: bf16 / split [B][C] with the pad columns 0
+  float* out_f32 = nullptr;  // nullable: [B][D]
+  int B = 1, S = 1, C = 8, D = 8;
+  // kvis / kend (both or neither; embed_tokens' key data, Sp = S rounded up to 32): the mean runs
+  // over the visible tokens only, sum / max(count, clip_min); a sample with none gets zeros (ONNX:
+  // NaN).  Without them: the mean of all S rows.
+  const float* kvis = nullptr;
+  const int* kend = nullptr;
+  int Sp = 0;
+  float clip_min = 0.f;
+  // normalize != 0: then v / max(||v||_2, eps) over the D columns (0 where that is 0 / 0).  With
+  // S = 1 this is a row normalisation alone.
+  int normalize = 0;
+  float eps = 0.f;
+  const long long* live = nullptr;
+  int split = 0;
+  // normalize with C > 64 hands the row over between its column blocks: ws >= pool_tokens_ws_bytes(B, C)
+  // bytes and B counters holding 0 (left at 0), neither shared with a launch that may run at the same
+  // time.
+  float* ws = nullptr;
+  size_t ws_bytes = 0;
+  int* counters = nullptr;
+  int counters_n = 0;
+};
+hipError_t pool_tokens(const PoolTokensArgs& a, hipStream_t s);
 int token_index_host(float x, int V);  // k::token_index on the host (tests)
 bool token_visible_host(float x, int op, float c, int neg, int trunc);  // k::token_visible on the host
 

@@ -1082,6 +1082,8 @@ inline int grid_for(long long work, int cap = 4096) {
   return static_cast<int>(g > cap ? cap : g);
 }
 
+inline bool misaligned(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; }
+
 }  // namespace
 
 namespace {
@@ -1134,7 +1136,6 @@ hipError_t layernorm_rows(const uint16_t* x, uint16_t* y, const float* gamma, co
 
 hipError_t rope_rows(const uint16_t* x, uint16_t* y, const float* cos, const float* sin, int B, int S, int H, int D,
                      int ldx, int ldy, hipStream_t s, int split) {
-  auto misaligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; };
   if (B <= 0 || S <= 0 || H <= 0 || !x || !y || !cos || !sin) return hipErrorInvalidValue;
   if (D != 32 && D != 64 && D != 80 && D != 96 && D != 128) return hipErrorInvalidValue;
   const long long W = static_cast<long long>(H) * D, rows = static_cast<long long>(B) * S;
@@ -1168,37 +1169,26 @@ hipError_t gather_rows(const uint16_t* x, uint16_t* y, int B, int S, int idx, in
 int token_index_host(float x, int V) { return token_index(x, V); }
 bool token_visible_host(float x, int op, float c, int neg, int trunc) { return token_visible(x, op, c, neg, trunc); }
 
-hipError_t embed_tokens(const float* ids, const float* table, int ldt, const float* pos, const float* type,
-                        uint16_t* out, int B, int S, int V, int C, hipStream_t s, int split, float* kvis, int* kend,
-                        int Sp, int pad_op, float pad_c, int pad_neg, int pad_trunc) {
-  auto misaligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; };
-  if (B <= 0 || S <= 0 || V <= 0 || C <= 0 || C % 8 || ldt < C || ldt % 4 || !ids || !table || !out ||
-      misaligned(table) || misaligned(pos) || misaligned(type) || misaligned(out))
+hipError_t embed_tokens(const EmbedArgs& a, hipStream_t s) {
+  const bool single = a.ld_in == 0 && !a.types && !a.mask;  // dense ids: the single-input kernel
+  if (a.B <= 0 || a.S <= 0 || a.V <= 0 || a.C <= 0 || a.C % 8 || a.ldt < a.C || a.ldt % 4 || !a.ids || !a.table ||
+      !a.out || (!single && a.ld_in < a.S) || misaligned(a.table) || misaligned(a.pos) || misaligned(a.ttab) ||
+      misaligned(a.out))
     return hipErrorInvalidValue;
-  if ((kvis == nullptr) != (kend == nullptr)) return hipErrorInvalidValue;
-  if (kvis && (Sp != (S + 31) / 32 * 32 || misaligned(kvis) || pad_op < 0 || pad_op > 2)) return hipErrorInvalidValue;
-  const int eblocks = grid_for(static_cast<long long>(B) * S * (C / 8));
-  hipLaunchKernelGGL(embed_tokens_kernel, dim3(eblocks + (kvis ? B : 0)), dim3(256), 0, s, ids, table, ldt, pos, type,
-                     out, B, S, V, C, split, eblocks, kvis, kend, Sp, pad_op, pad_c, pad_neg, pad_trunc);
-  return hipGetLastError();
-}
-
-hipError_t embed_inputs(const float* ids, const float* types, const float* mask, int ld_in, const float* table, int ldt,
-                        const float* pos, const float* ttab, int ldtt, int T, uint16_t* out, int B, int S, int V, int C,
-                        hipStream_t s, int split, float* kvis, int* kend, int Sp, int pad_op, float pad_c, int pad_neg,
-                        int pad_trunc) {
-  auto misaligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; };
-  if (B <= 0 || S <= 0 || V <= 0 || C <= 0 || C % 8 || ldt < C || ldt % 4 || !ids || !table || !out || ld_in < S ||
-      misaligned(table) || misaligned(pos) || misaligned(ttab) || misaligned(out))
+  if (a.types && (!a.ttab || a.T <= 0 || a.ldtt < a.C || a.ldtt % 4)) return hipErrorInvalidValue;
+  if ((a.kvis == nullptr) != (a.kend == nullptr)) return hipErrorInvalidValue;
+  if (a.mask && !a.kvis) return hipErrorInvalidValue;  // a mask has no other reader
+  if (a.kvis && (a.Sp != (a.S + 31) / 32 * 32 || misaligned(a.kvis) || a.pad_op < 0 || a.pad_op > 2))
     return hipErrorInvalidValue;
-  if (types && (!ttab || T <= 0 || ldtt < C || ldtt % 4)) return hipErrorInvalidValue;
-  if ((kvis == nullptr) != (kend == nullptr)) return hipErrorInvalidValue;
-  if (mask && !kvis) return hipErrorInvalidValue;  // a mask has no other reader
-  if (kvis && (Sp != (S + 31) / 32 * 32 || misaligned(kvis) || pad_op < 0 || pad_op > 2)) return hipErrorInvalidValue;
-  const int eblocks = grid_for(static_cast<long long>(B) * S * (C / 8));
-  hipLaunchKernelGGL(embed_inputs_kernel, dim3(eblocks + (kvis ? B : 0)), dim3(256), 0, s, ids, types, mask, ld_in, table,
-                     ldt, pos, ttab, ldtt, T, out, B, S, V, C, split, eblocks, kvis, kend, Sp, pad_op, pad_c, pad_neg,
-                     pad_trunc);
+  const int eblocks = grid_for(static_cast<long long>(a.B) * a.S * (a.C / 8));
+  const dim3 grid(eblocks + (a.kvis ? a.B : 0));
+  if (single)
+    hipLaunchKernelGGL(embed_tokens_kernel, grid, dim3(256), 0, s, a.ids, a.table, a.ldt, a.pos, a.ttab, a.out, a.B, a.S,
+                       a.V, a.C, a.split, eblocks, a.kvis, a.kend, a.Sp, a.pad_op, a.pad_c, a.pad_neg, a.pad_trunc);
+  else
+    hipLaunchKernelGGL(embed_inputs_kernel, grid, dim3(256), 0, s, a.ids, a.types, a.mask, a.ld_in, a.table, a.ldt, a.pos,
+                       a.ttab, a.ldtt, a.T, a.out, a.B, a.S, a.V, a.C, a.split, eblocks, a.kvis, a.kend, a.Sp, a.pad_op,
+                       a.pad_c, a.pad_neg, a.pad_trunc);
   return hipGetLastError();
 }
 
@@ -1206,21 +1196,19 @@ size_t pool_tokens_ws_bytes(int B, int C) {
   return static_cast<size_t>(B) * (C + (C + kPoolCols - 1) / kPoolCols) * 4;
 }
 
-hipError_t pool_tokens(const uint16_t* x, uint16_t* out, float* out_f32, int B, int S, int C, int D, const float* kvis,
-                       const int* kend, int Sp, float clip_min, int normalize, float eps, hipStream_t s,
-                       const long long* live, int split, float* ws, size_t ws_bytes, int* counters, int counters_n) {
-  auto misaligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; };
-  if (B <= 0 || S <= 0 || C <= 0 || C % 8 || D <= 0 || D > C || !x || (!out && !out_f32) || misaligned(x) || B > 65535 ||
-      !(clip_min >= 0.f) || !(eps >= 0.f))
+hipError_t pool_tokens(const PoolTokensArgs& a, hipStream_t s) {
+  if (a.B <= 0 || a.S <= 0 || a.C <= 0 || a.C % 8 || a.D <= 0 || a.D > a.C || !a.x || (!a.out && !a.out_f32) ||
+      misaligned(a.x) || a.B > 65535 || !(a.clip_min >= 0.f) || !(a.eps >= 0.f))
     return hipErrorInvalidValue;
-  if ((kvis == nullptr) != (kend == nullptr)) return hipErrorInvalidValue;
-  if (kvis && Sp != (S + 31) / 32 * 32) return hipErrorInvalidValue;
-  const int ns = (C + kPoolCols - 1) / kPoolCols;
-  if (normalize && ns > 1 &&
-      (!ws || !counters || counters_n < B || pool_tokens_ws_bytes(B, C) > ws_bytes || pool_tokens_ws_bytes(B, C) >> 31))
+  if ((a.kvis == nullptr) != (a.kend == nullptr)) return hipErrorInvalidValue;
+  if (a.kvis && a.Sp != (a.S + 31) / 32 * 32) return hipErrorInvalidValue;
+  const int ns = (a.C + kPoolCols - 1) / kPoolCols;
+  if (a.normalize && ns > 1 &&
+      (!a.ws || !a.counters || a.counters_n < a.B || pool_tokens_ws_bytes(a.B, a.C) > a.ws_bytes ||
+       pool_tokens_ws_bytes(a.B, a.C) >> 31))
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(pool_tokens_kernel, dim3(ns, B), dim3(256), 0, s, x, out, out_f32, S, C, D, kvis, kend, Sp, clip_min,
-                     normalize, eps, live, split, ws, counters);
+  hipLaunchKernelGGL(pool_tokens_kernel, dim3(ns, a.B), dim3(256), 0, s, a.x, a.out, a.out_f32, a.S, a.C, a.D, a.kvis,
+                     a.kend, a.Sp, a.clip_min, a.normalize, a.eps, a.live, a.split, a.ws, a.counters);
   return hipGetLastError();
 }
 
@@ -1247,10 +1235,17 @@ int g_attn_variant = 0;  // 0: K/V staged one tile ahead, 1: two tiles ahead (DE
 }
 void set_attention_variant(int v) { g_attn_variant = v; }
 
-hipError_t attention(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, int B, int S, int H,
-                     int D, int ldq, int ldk, int ldv, int ldo, float scale, hipStream_t s, int split,
-                     const float* bias, int bias_heads, int Sp, int causal, const float* kvis, const int* kend,
-                     int kv_heads) {
+hipError_t attention(const AttentionArgs& a, hipStream_t s) {
+  // the kernels' arguments under the names the launch macros below use
+  const uint16_t *q = a.q, *k = a.k, *v = a.v;
+  uint16_t* out = a.out;
+  const int B = a.B, S = a.S, H = a.H, D = a.D, ldq = a.ldq, ldk = a.ldk, ldv = a.ldv, ldo = a.ldo, split = a.split;
+  const float scale = a.scale;
+  const float* bias = a.bias;
+  const int bias_heads = a.bias_heads, Sp = a.Sp, causal = a.causal;
+  const float* kvis = a.kvis;
+  const int* kend = a.kend;
+  int kv_heads = a.kv_heads;
   const bool masked = bias != nullptr || causal != 0 || kvis != nullptr;
   if (!attention_supported(D, S, masked) || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4) return hipErrorInvalidValue;
   if (kv_heads < 0 || kv_heads > H) return hipErrorInvalidValue;

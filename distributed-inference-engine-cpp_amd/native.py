@@ -722,13 +722,9 @@ def _sig_kernels():
     L.die_pair_permute_row.argtypes = [i]
     L.die_kern_input_prep.argtypes = [u64] * 4 + [i] * 5 + [u64, i]
     L.die_kern_pool2d.restype = i
-    L.die_kern_pool2d.argtypes = [u64, u64] + [i] * 14 + [u64, i]
+    L.die_kern_pool2d.argtypes = [u64, u64] + [i] * 14 + [u64, i, u64, u64, u64, i]
     L.die_kern_gap.restype = i
-    L.die_kern_gap.argtypes = [u64] * 5 + [i] * 4 + [u64, i]
-    L.die_kern_pool2d_ex.restype = i
-    L.die_kern_pool2d_ex.argtypes = [u64, u64] + [i] * 14 + [u64, i, u64, u64, u64, i]
-    L.die_kern_gap_ex.restype = i
-    L.die_kern_gap_ex.argtypes = [u64] * 5 + [i] * 4 + [u64, i, u64, i]
+    L.die_kern_gap.argtypes = [u64] * 5 + [i] * 4 + [u64, i, u64, i]
     ll, f = C.c_longlong, C.c_float
     L.die_kern_rows_prep.restype = i
     L.die_kern_rows_prep.argtypes = [u64, u64, ll, i, i, u64, i]
@@ -767,31 +763,16 @@ def _sig_kernels():
     L.die_kern_softmax.restype = i
     L.die_kern_softmax.argtypes = [u64, u64, u64, C.c_longlong, i, u64, i]
     L.die_kern_layernorm.restype = i
-    L.die_kern_layernorm.argtypes = [u64] * 4 + [C.c_float, C.c_longlong, i, u64, i, i]
-    L.die_kern_layernorm_ex.restype = i
-    L.die_kern_layernorm_ex.argtypes = [u64] * 4 + [C.c_float, C.c_longlong, i, u64, i, i, i, u64, i]
+    L.die_kern_layernorm.argtypes = [u64] * 4 + [C.c_float, C.c_longlong, i, u64, i, i, i, u64, i]
     L.die_kern_rope_rows.restype = i
     L.die_kern_rope_rows.argtypes = [u64] * 4 + [i] * 6 + [u64, i]
     L.die_kern_tokens.restype = i
     L.die_kern_tokens.argtypes = [u64] * 4 + [i] * 3 + [u64, i]
     L.die_kern_gather_rows.restype = i
     L.die_kern_gather_rows.argtypes = [u64, u64] + [i] * 4 + [u64, i]
-    L.die_kern_attention.restype = i
-    L.die_kern_attention.argtypes = [u64] * 4 + [i] * 8 + [C.c_float, u64, i]
-    L.die_kern_attention_masked.restype = i
-    L.die_kern_attention_masked.argtypes = [u64] * 4 + [i] * 8 + [C.c_float, u64, i, u64, i, i, i]
-    L.die_kern_attention_keymask.restype = i
-    L.die_kern_attention_keymask.argtypes = [u64] * 4 + [i] * 8 + [C.c_float, u64, i, u64, i, i, i, u64, u64]
-    L.die_kern_attention_gqa.restype = i
-    L.die_kern_attention_gqa.argtypes = [u64] * 4 + [i] * 8 + [C.c_float, u64, i, u64, i, i, i, u64, u64, i]
-    L.die_kern_embed_tokens.restype = i
-    L.die_kern_embed_tokens.argtypes = [u64, u64, i, u64, u64, u64, i, i, i, i, u64, i, u64, u64, i, i, C.c_float, i, i]
-    L.die_kern_embed_inputs.restype = i
-    L.die_kern_embed_inputs.argtypes = [u64, u64, u64, i, u64, i, u64, u64, i, i, u64, i, i, i, i, u64, i, u64, u64, i, i,
-                                        C.c_float, i, i]
-    L.die_kern_pool_tokens.restype = i
-    L.die_kern_pool_tokens.argtypes = [u64, u64, u64, i, i, i, i, u64, u64, i, C.c_float, i, C.c_float, u64, u64, i,
-                                       u64, u64, u64, i]
+    for fn in (L.die_kern_attention, L.die_kern_embed_tokens, L.die_kern_pool_tokens):  # (geometry(...), stream)
+        fn.restype = i
+        fn.argtypes = [C.c_char_p, u64]
     L.die_kern_pool_tokens_ws_bytes.restype = u64
     L.die_kern_pool_tokens_ws_bytes.argtypes = [i, i]
     L.die_token_index.restype = i
@@ -812,11 +793,17 @@ def _sig_kernels():
     L.die_decode_scratch_bytes.restype = C.c_longlong
     L.die_decode_scratch_bytes.argtypes = [i, C.c_longlong]
     L.die_kern_decode.restype = i
-    L.die_kern_decode.argtypes = [u64, u64, C.c_longlong, u64, i, u64, C.c_longlong, u64, u64, u64, u64]
-    L.die_kern_decode_packed.restype = i
-    L.die_kern_decode_packed.argtypes = [u64, u64, u64, u64, C.c_longlong, u64, i, u64, C.c_longlong, u64, u64, u64, u64]
+    L.die_kern_decode.argtypes = [u64, u64, u64, u64, C.c_longlong, u64, i, u64, C.c_longlong, u64, u64, u64, u64]
     L._kern_sigs = True
     return L
+
+
+def geometry(members: Dict[str, Any]) -> bytes:
+    """The geometry JSON of die_kern_attention / _embed_tokens / _pool_tokens: keys = the members of
+    the launcher's argument struct (kernels.h), device addresses as ints; a key left out keeps the
+    member's default, an unknown one fails the call.  json prints a float with repr(), every digit
+    of the double, so it reaches the launcher rounded to fp32 once, as a c_float argument would."""
+    return json.dumps(members).encode()
 
 
 def plan_summary(model_path: str, max_batch: int = 32, side_branches: bool = False,

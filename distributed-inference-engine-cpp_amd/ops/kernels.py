@@ -305,9 +305,9 @@ def pool2d_nhwc(x, k, stride, pad, is_max=True, count_include_pad=False, split=F
     Wo = (W + 2 * pw - kw) // sw + 1
     y = _storage(out, (B, Ho, Wo, C), split, x.device)
     xin, sc, sf, lv = _in(x, split), _f32(scale), _f32(shift), _live(live, x.device)
-    rc = native.kernels().die_kern_pool2d_ex(_ptr(xin), _ptr(y), B, H, W, C, Ho, Wo, kh, kw, sh, sw, ph, pw,
-                                             int(is_max), int(count_include_pad), _stream(), int(split), _ptr(lv),
-                                             _ptr(sc), _ptr(sf), int(act))
+    rc = native.kernels().die_kern_pool2d(_ptr(xin), _ptr(y), B, H, W, C, Ho, Wo, kh, kw, sh, sw, ph, pw,
+                                          int(is_max), int(count_include_pad), _stream(), int(split), _ptr(lv),
+                                          _ptr(sc), _ptr(sf), int(act))
     _check(rc, "pool2d")
     return _out(y, split)
 
@@ -320,8 +320,8 @@ def global_avgpool_nhwc(x, scale=None, shift=None, relu=False, split=False, mode
     o = _storage(out, (B, C), split, x.device)
     out32 = torch.empty((B, C), dtype=torch.float32, device=x.device)
     xin, lv = _in(x, split), _live(live, x.device)
-    rc = native.kernels().die_kern_gap_ex(_ptr(xin), _ptr(o), _ptr(out32), _ptr(scale), _ptr(shift),
-                                          int(relu), B, H * W, C, _stream(), int(split), _ptr(lv), int(mode))
+    rc = native.kernels().die_kern_gap(_ptr(xin), _ptr(o), _ptr(out32), _ptr(scale), _ptr(shift),
+                                       int(relu), B, H * W, C, _stream(), int(split), _ptr(lv), int(mode))
     _check(rc, "global_avgpool")
     return _out(o, split), out32
 
@@ -356,15 +356,7 @@ def linear(x, w, bias=None, act=0, res=None, tile=-1, splits=1, split=False):
 
 
 def layernorm(x, gamma, beta, eps=1e-5, split=False, variant=0):
-    import torch
-
-    C = x.shape[-1]
-    y = torch.empty(((2,) if split else ()) + tuple(x.shape), dtype=torch.bfloat16, device=x.device)
-    xin, gm, bt = _in(x, split), gamma.float().contiguous(), beta.float().contiguous()
-    rc = native.kernels().die_kern_layernorm(_ptr(xin), _ptr(y), _ptr(gm), _ptr(bt), float(eps), x.numel() // C, C, _stream(),
-                                             int(split), int(variant))
-    _check(rc, "layernorm")
-    return _out(y, split)
+    return layernorm_rows(x, gamma, beta, eps, split, variant)
 
 
 def layernorm_rows(x, gamma, beta=None, eps=1e-5, split=False, variant=0, cl=0, stats=False, rms=False):
@@ -380,8 +372,8 @@ def layernorm_rows(x, gamma, beta=None, eps=1e-5, split=False, variant=0, cl=0, 
     st = torch.empty((rows, 2), dtype=torch.float32, device=x.device) if stats else None
     xin, gm = _in(x, split), gamma.float().contiguous()
     bt = None if beta is None else beta.float().contiguous()
-    rc = native.kernels().die_kern_layernorm_ex(_ptr(xin), 0 if stats else _ptr(y), _ptr(gm), _ptr(bt), float(eps), rows, C,
-                                                _stream(), int(split), int(cl), int(variant), _ptr(st), int(rms))
+    rc = native.kernels().die_kern_layernorm(_ptr(xin), 0 if stats else _ptr(y), _ptr(gm), _ptr(bt), float(eps), rows, C,
+                                             _stream(), int(split), int(cl), int(variant), _ptr(st), int(rms))
     _check(rc, "layernorm_rows")
     return st if stats else _out(y, split)
 
@@ -449,57 +441,14 @@ def embed_tokens(ids, table, pos=None, type_row=None, pad_test=None, split=False
     visible key (0: none); else (rows, None, None).
     A table whose rows are 16-byte aligned with a pitch that is a multiple of 4 and >= Dp is read in
     place (a row slice of a larger table, say); any other is copied to pitch Dp.
-    Models with attention_mask / token_type_ids inputs (the embed_inputs entry point; without any of
-    the following the single-input entry point runs as before):
+    Models with attention_mask / token_type_ids inputs (request rows of several segments; without any
+    of the following the ids are read densely by the single-input kernel, as before):
     types [B, S] + type_table [T, D]: rows += type_table[idx(types[b, s])] (the same clamp against T;
     the table is read in place under the same rule as `table`); excludes type_row.
     mask [B, S]: the key data comes from the mask, a key is visible where mask != 0 (mask_trunc: where
     trunc(mask) != 0, an integer-declared mask input); excludes pad_test.
     packed = dict(S=, ids=, types=, mask=): `ids` is ONE tensor [B, L] of request rows holding the
     segments at these element offsets (types / mask: None = absent), read in place with pitch L."""
-    import torch
-
-    if types is not None or mask is not None or packed is not None:
-        return _embed_inputs(ids, table, pos, type_row, pad_test, split, types, type_table, mask, mask_trunc, packed)
-    B, S = ids.shape
-    V, D = table.shape
-    Dp = (D + 7) // 8 * 8
-    dev = table.device
-    idf = ids.to(device=dev, dtype=torch.float32).contiguous()
-
-    def padded(t, rows):
-        if t is None:
-            return None
-        t = t.to(device=dev, dtype=torch.float32).reshape(rows, D)
-        if Dp == D:
-            return t.contiguous()
-        o = torch.zeros((rows, Dp), dtype=torch.float32, device=dev)
-        o[:, :D] = t
-        return o
-
-    if (table.dtype == torch.float32 and table.dim() == 2 and table.stride(1) == 1 and table.stride(0) >= Dp
-            and table.stride(0) % 4 == 0 and table.data_ptr() % 16 == 0):
-        tab, ldt = table, int(table.stride(0))
-    else:
-        tab, ldt = padded(table, V), Dp
-    ps, ty = padded(pos, S), padded(type_row, 1)
-    out = torch.empty(((2,) if split else ()) + (B, S, Dp), dtype=torch.bfloat16, device=dev)
-    kvis = kend = None
-    Sp = op = neg = 0
-    val = 0.0
-    if pad_test is not None:
-        name, val = pad_test if isinstance(pad_test, (tuple, list)) else ("eq", pad_test)
-        op, neg = _PAD_OPS[name], 1  # visible = not (id op value)
-        Sp = (S + 31) // 32 * 32
-        kvis = torch.empty((B, Sp), dtype=torch.float32, device=dev)
-        kend = torch.empty((B,), dtype=torch.int32, device=dev)
-    rc = native.kernels().die_kern_embed_tokens(_ptr(idf), _ptr(tab), ldt, _ptr(ps), _ptr(ty), _ptr(out), B, S, V, Dp,
-                                                _stream(), int(split), _ptr(kvis), _ptr(kend), Sp, op, float(val), neg, 0)
-    _check(rc, "embed_tokens")
-    return _out(out, split), kvis, kend
-
-
-def _embed_inputs(ids, table, pos, type_row, pad_test, split, types, type_table, mask, mask_trunc, packed):
     import torch
 
     dev = table.device
@@ -511,14 +460,15 @@ def _embed_inputs(ids, table, pos, type_row, pad_test, split, types, type_table,
                 packed[name] = S * len(parts)
                 parts.append(t)
         rows = torch.cat([t.to(device=dev, dtype=torch.float32) for t in parts], dim=1).contiguous()
+        L = rows.shape[1] if len(parts) > 1 else 0  # ld_in = 0: dense ids, the single-input kernel
     else:
         rows = ids.to(device=dev, dtype=torch.float32).contiguous()
-        B, S = rows.shape[0], int(packed["S"])
-    L = rows.shape[1]
+        B, S, L = rows.shape[0], int(packed["S"]), rows.shape[1]
     o_ids, o_types, o_mask = packed["ids"], packed.get("types"), packed.get("mask")
     for off in (o_ids, o_types, o_mask):  # the kernel reads [off, off + S) of every row: keep it inside
-        if off is not None and not (0 <= int(off) and int(off) + S <= L):
-            raise ValueError("embed_tokens: segment offset %r with S = %d outside the request row of %d" % (off, S, L))
+        if off is not None and not (0 <= int(off) and int(off) + S <= rows.shape[1]):
+            raise ValueError("embed_tokens: segment offset %r with S = %d outside the request row of %d"
+                             % (off, S, rows.shape[1]))
     if (o_types is not None) != (type_table is not None) or (o_types is not None and type_row is not None):
         raise ValueError("embed_tokens: a type input needs type_table and excludes type_row")
     if o_mask is not None and pad_test is not None:
@@ -537,8 +487,6 @@ def _embed_inputs(ids, table, pos, type_row, pad_test, split, types, type_table,
         return o
 
     def in_place(t):
-        if t is None:
-            return None, 0
         if (t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= Dp and t.stride(0) % 4 == 0
                 and t.data_ptr() % 16 == 0):
             return t, int(t.stride(0))
@@ -560,7 +508,7 @@ def _embed_inputs(ids, table, pos, type_row, pad_test, split, types, type_table,
         op, val, neg = 0, 0.0, 1  # visible = not (mask == 0)
     elif pad_test is not None:
         name, val = pad_test if isinstance(pad_test, (tuple, list)) else ("eq", pad_test)
-        op, neg = _PAD_OPS[name], 1
+        op, neg = _PAD_OPS[name], 1  # visible = not (id op value)
     if o_mask is not None or pad_test is not None:
         Sp = (S + 31) // 32 * 32
         kvis = torch.empty((B, Sp), dtype=torch.float32, device=dev)
@@ -570,11 +518,11 @@ def _embed_inputs(ids, table, pos, type_row, pad_test, split, types, type_table,
     def seg(off):
         return 0 if off is None else base + 4 * int(off)
 
-    rc = native.kernels().die_kern_embed_inputs(seg(o_ids), seg(o_types), seg(o_mask), L, _ptr(tab), ldt, _ptr(ps),
-                                                _ptr(ttab), ldtt, T, _ptr(out), B, S, V, Dp, _stream(), int(split),
-                                                _ptr(kvis), _ptr(kend), Sp, op, float(val), neg,
-                                                int(bool(mask_trunc) and o_mask is not None))
-    _check(rc, "embed_tokens")
+    geom = dict(ids=seg(o_ids), types=seg(o_types), mask=seg(o_mask), ld_in=int(L), table=_ptr(tab), ldt=ldt, pos=_ptr(ps),
+                ttab=_ptr(ttab), ldtt=ldtt, T=int(T), out=_ptr(out), B=B, S=S, V=V, C=Dp, split=int(split),
+                kvis=_ptr(kvis), kend=_ptr(kend), Sp=Sp, pad_op=op, pad_c=float(val), pad_neg=neg,
+                pad_trunc=int(bool(mask_trunc) and o_mask is not None))
+    _check(native.kernels().die_kern_embed_tokens(native.geometry(geom), _stream()), "embed_tokens")
     return _out(out, split), kvis, kend
 
 
@@ -619,10 +567,10 @@ def pool_tokens(x, key_mask=None, clip_min=0.0, normalize=False, eps=1e-12, spli
     ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=dev)
     if counters is None:
         counters = torch.zeros((B,), dtype=torch.int32, device=dev)
-    rc = L.die_kern_pool_tokens(_ptr(xin), _ptr(out), _ptr(out32), B, S, C, D, _ptr(kvis), _ptr(kend), Sp, float(clip_min),
-                                int(normalize), float(eps), _stream(), 0, int(split), _ptr(ws), ws_bytes,
-                                _ptr(counters), int(counters.numel()))
-    _check(rc, "pool_tokens")
+    geom = dict(x=_ptr(xin), out=_ptr(out), out_f32=_ptr(out32), B=B, S=S, C=C, D=D, kvis=_ptr(kvis), kend=_ptr(kend), Sp=Sp,
+                clip_min=float(clip_min), normalize=int(normalize), eps=float(eps), split=int(split), ws=_ptr(ws),
+                ws_bytes=ws_bytes, counters=_ptr(counters), counters_n=int(counters.numel()))
+    _check(L.die_kern_pool_tokens(native.geometry(geom), _stream()), "pool_tokens")
     return _out(out, split), out32
 
 
@@ -648,37 +596,20 @@ def _attention_bias(bias, S, heads, pad=0.0):
 
 def _attention_launch(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, split, bias, causal, what, key_mask=None,
                       kv_heads=None, bias_pad=0.0):
-    if kv_heads is not None:  # the entry point with kv_heads (grouped-query attention), whatever the masks
-        kvis = kend = None
-        Sp = (S + 31) // 32 * 32
-        if key_mask is not None:
-            if not isinstance(key_mask, (tuple, list)) and tuple(key_mask.shape) != (B, S):
-                raise ValueError("key mask must be bool [B, S] = [%d, %d], got %s" % (B, S, tuple(key_mask.shape)))
-            kvis, kend = key_mask if isinstance(key_mask, (tuple, list)) else key_mask_data(key_mask)
-            if tuple(kvis.shape) != (B, Sp) or tuple(kend.shape) != (B,):
-                raise ValueError("key mask must be bool [B, S] or (kvis [B, Sp] fp32, kend [B] int32), B = %d, S = %d" % (B, S))
-        table, hb, _ = _attention_bias(bias, S, heads, bias_pad) if bias is not None else (None, 0, 0)
-        rc = native.kernels().die_kern_attention_gqa(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, _stream(), split,
-                                                     _ptr(table), hb, Sp if (table is not None or kvis is not None) else 0,
-                                                     int(bool(causal)), _ptr(kvis), _ptr(kend), int(kv_heads))
-    elif key_mask is not None:
+    kvis = kend = table = None
+    hb = 0
+    if key_mask is not None:
         if not isinstance(key_mask, (tuple, list)) and tuple(key_mask.shape) != (B, S):
             raise ValueError("key mask must be bool [B, S] = [%d, %d], got %s" % (B, S, tuple(key_mask.shape)))
         kvis, kend = key_mask if isinstance(key_mask, (tuple, list)) else key_mask_data(key_mask)
-        Sp = (S + 31) // 32 * 32
-        if tuple(kvis.shape) != (B, Sp) or tuple(kend.shape) != (B,):
+        if tuple(kvis.shape) != (B, (S + 31) // 32 * 32) or tuple(kend.shape) != (B,):
             raise ValueError("key mask must be bool [B, S] or (kvis [B, Sp] fp32, kend [B] int32), B = %d, S = %d" % (B, S))
-        table, hb, _ = _attention_bias(bias, S, heads, bias_pad) if bias is not None else (None, 0, 0)
-        rc = native.kernels().die_kern_attention_keymask(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, _stream(),
-                                                         split, _ptr(table), hb, Sp, int(bool(causal)), _ptr(kvis),
-                                                         _ptr(kend))
-    elif bias is None and not causal:  # the unmasked entry point, as before
-        rc = native.kernels().die_kern_attention(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, _stream(), split)
-    else:
-        table, hb, Sp = _attention_bias(bias, S, heads, bias_pad) if bias is not None else (None, 0, 0)
-        rc = native.kernels().die_kern_attention_masked(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, sc, _stream(),
-                                                        split, _ptr(table), hb, Sp, int(bool(causal)))
-    _check(rc, what)
+    if bias is not None:
+        table, hb, _ = _attention_bias(bias, S, heads, bias_pad)
+    geom = dict(q=q, k=k, v=v, out=out, B=B, S=S, H=heads, D=D, ldq=ldq, ldk=ldk, ldv=ldv, ldo=ldo, scale=sc, split=split,
+                bias=_ptr(table), bias_heads=hb, Sp=(S + 31) // 32 * 32 if (table is not None or kvis is not None) else 0,
+                causal=int(bool(causal)), kvis=_ptr(kvis), kend=_ptr(kend), kv_heads=0 if kv_heads is None else int(kv_heads))
+    _check(native.kernels().die_kern_attention(native.geometry(geom), _stream()), what)
 
 
 def attention_launch(q, k, v, out, B, S, heads, D, ldq, ldk, ldv, ldo, scale, split=False, bias=None, causal=False,
@@ -798,6 +729,7 @@ def decode_json_numbers(texts, numel, text_cap=None, slot_order=None, packed=Fal
     status = torch.full((B,), -7, dtype=torch.int32, device="cuda")
     ntok = torch.zeros(B, dtype=torch.int32, device="cuda")
     scratch = torch.empty(int(L.die_decode_scratch_bytes(B, text_cap)), dtype=torch.uint8, device="cuda")
+    d_packed = d_poffs = None
     if packed:
         hp = np.zeros(nslots * text_cap // 2, np.uint8)
         poffs = np.full(B, -1, np.int64)
@@ -810,11 +742,8 @@ def decode_json_numbers(texts, numel, text_cap=None, slot_order=None, packed=Fal
         d_poffs = torch.from_numpy(poffs).cuda()
         if d_offs is None:
             d_offs = torch.from_numpy(offs).cuda()
-        rc = L.die_kern_decode_packed(_ptr(d_text), _ptr(d_offs), _ptr(d_packed), _ptr(d_poffs), text_cap, _ptr(d_lens),
-                                      B, _ptr(out), numel, _ptr(status), _ptr(ntok), _ptr(scratch), _stream())
-    else:
-        rc = L.die_kern_decode(_ptr(d_text), _ptr(d_offs), text_cap, _ptr(d_lens), B, _ptr(out), numel, _ptr(status),
-                               _ptr(ntok), _ptr(scratch), _stream())
+    rc = L.die_kern_decode(_ptr(d_text), _ptr(d_offs), _ptr(d_packed), _ptr(d_poffs), text_cap, _ptr(d_lens), B, _ptr(out),
+                           numel, _ptr(status), _ptr(ntok), _ptr(scratch), _stream())
     _check(rc, "decode_json_numbers")
     return out, status, ntok
 

@@ -115,6 +115,6 @@ def test_generic_kernel_entries_resolve(native):
     """The C-ABI entries behind the wrappers of ops/kernels.py exist and have their signatures declared."""
     L = native.kernels()
     for name in ("rows_prep", "input_prep_wide", "copy_cols", "binary_rows", "unary_rows", "where_rows", "resize_nhwc",
-                 "pad_nhwc", "rows_to_f32", "nhwc_to_nchw_strided", "bmm_rows", "pool2d_ex", "gap_ex"):
+                 "pad_nhwc", "rows_to_f32", "nhwc_to_nchw_strided", "bmm_rows", "pool2d", "gap"):
         fn = getattr(L, "die_kern_" + name)
         assert fn.argtypes, name

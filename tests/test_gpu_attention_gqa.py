@@ -180,8 +180,10 @@ def test_gqa_launcher_rejects_bad_arguments(K):
 
     def call(H=4, Hkv=2, D=64, bias=0, bias_heads=0, Sp=0, causal=0, kv=0, ke=0, koff=0):
         ldkv = (Hkv if Hkv > 0 else H) * D
-        return L.die_kern_attention_gqa(x.data_ptr(), x.data_ptr() + koff, x.data_ptr(), out.data_ptr(), Bn, S, H, D, H * D,
-                                        ldkv, ldkv, H * D, 0.125, st, 0, bias, bias_heads, Sp, causal, kv, ke, Hkv)
+        return L.die_kern_attention(native.geometry(dict(
+            q=x.data_ptr(), k=x.data_ptr() + koff, v=x.data_ptr(), out=out.data_ptr(), B=Bn, S=S, H=H, D=D, ldq=H * D,
+            ldk=ldkv, ldv=ldkv, ldo=H * D, scale=0.125, split=0, bias=bias, bias_heads=bias_heads, Sp=Sp, causal=causal,
+            kvis=kv, kend=ke, kv_heads=Hkv)), st)
 
     assert call() == 0 and call(causal=1) == 0
     assert call(Sp=64, kv=kvis.data_ptr(), ke=kend.data_ptr()) == 0

@@ -205,8 +205,9 @@ def test_keymask_launcher_rejects_bad_arguments(K):
     st = torch.cuda.current_stream().cuda_stream
 
     def call(Sp=64, causal=0, kv=kvis.data_ptr(), ke=kend.data_ptr()):
-        return L.die_kern_attention_keymask(x.data_ptr(), x.data_ptr(), x.data_ptr(), out.data_ptr(), Bn, S, H, D, C, C, C,
-                                            C, 0.125, st, 0, 0, 0, Sp, causal, kv, ke)
+        return L.die_kern_attention(native.geometry(dict(
+            q=x.data_ptr(), k=x.data_ptr(), v=x.data_ptr(), out=out.data_ptr(), B=Bn, S=S, H=H, D=D, ldq=C, ldk=C, ldv=C,
+            ldo=C, scale=0.125, split=0, bias=0, bias_heads=0, Sp=Sp, causal=causal, kvis=kv, kend=ke)), st)
 
     assert call() == 0
     assert call(causal=1) != 0

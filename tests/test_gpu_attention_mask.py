@@ -166,8 +166,9 @@ def test_masked_attention_rejects_bad_arguments(K):
     st = torch.cuda.current_stream().cuda_stream
 
     def call(bias_heads, Sp, ptr=bias.data_ptr()):
-        return L.die_kern_attention_masked(x.data_ptr(), x.data_ptr(), x.data_ptr(), out.data_ptr(), B, S, H, D, C, C,
-                                           C, C, 0.125, st, 0, ptr, bias_heads, Sp, 0)
+        return L.die_kern_attention(native.geometry(dict(
+            q=x.data_ptr(), k=x.data_ptr(), v=x.data_ptr(), out=out.data_ptr(), B=B, S=S, H=H, D=D, ldq=C, ldk=C, ldv=C,
+            ldo=C, scale=0.125, split=0, bias=ptr, bias_heads=bias_heads, Sp=Sp, causal=0)), st)
 
     assert call(1, 64) == 0 and call(H, 64) == 0
     assert call(1, 40) != 0 and call(1, 96) != 0  # Sp must be 64 for S = 40

@@ -168,8 +168,10 @@ def test_embed_inputs_rejects_bad_arguments(K):
 
     def call(ld=3 * S, types=base + 4 * 2 * S, mask=base + 4 * S, tt=ttab.data_ptr(), T=T, ldtt=C, kv=kvis.data_ptr(),
              ke=kend.data_ptr(), Sp=64):
-        return L.die_kern_embed_inputs(base, types, mask, ld, table.data_ptr(), C, 0, tt, ldtt, T, out.data_ptr(), Bn, S, V,
-                                       C, st, 0, kv, ke, Sp, 0, 0.0, 1, 0)
+        return L.die_kern_embed_tokens(native.geometry(dict(
+            ids=base, types=types, mask=mask, ld_in=ld, table=table.data_ptr(), ldt=C, pos=0, ttab=tt, ldtt=ldtt, T=T,
+            out=out.data_ptr(), B=Bn, S=S, V=V, C=C, split=0, kvis=kv, kend=ke, Sp=Sp, pad_op=0, pad_c=0.0, pad_neg=1,
+            pad_trunc=0)), st)
 
     bad = [call(ld=S - 1), call(T=0), call(T=-1), call(tt=ttab.data_ptr() + 4), call(tt=0), call(ldtt=16), call(ldtt=34),
            call(ke=0), call(kv=0), call(kv=0, ke=0, Sp=0), call(Sp=40)]  # (a mask without key data has no reader)

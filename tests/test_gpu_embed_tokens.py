@@ -152,8 +152,9 @@ def test_embed_tokens_rejects_bad_arguments(K):
     kend = torch.empty(Bn, device="cuda", dtype=torch.int32)
 
     def call(C=C, ldt=C, Sp=64, kv=kvis.data_ptr(), ke=kend.data_ptr(), tab=table.data_ptr(), op=0):
-        return L.die_kern_embed_tokens(ids.data_ptr(), tab, ldt, 0, 0, out.data_ptr(), Bn, S, V, C, st, 0, kv, ke, Sp, op, 0.0,
-                                       1, 0)
+        return L.die_kern_embed_tokens(native.geometry(dict(
+            ids=ids.data_ptr(), table=tab, ldt=ldt, pos=0, ttab=0, out=out.data_ptr(), B=Bn, S=S, V=V, C=C, split=0, kvis=kv,
+            kend=ke, Sp=Sp, pad_op=op, pad_c=0.0, pad_neg=1, pad_trunc=0)), st)
 
     assert call() == 0
     assert call(C=20) != 0 and call(ldt=16) != 0 and call(ldt=34) != 0  # stored width % 8, table pitch

@@ -108,20 +108,17 @@ def main():
                 out = torch.empty((B, S, C), dtype=torch.bfloat16, device="cuda")
             base = src.data_ptr()
 
+            geom = dict(q=base, k=base + 2 * C, v=base + 4 * C, out=out.data_ptr(), B=B, S=S, H=H, D=D, ldq=3 * C, ldk=3 * C,
+                        ldv=3 * C, ldo=C, scale=float(1 / np.sqrt(D)), split=int(split))
+            if mask == "keypad":
+                geom.update(Sp=Sp, kvis=kvis.data_ptr(), kend=kend.data_ptr())
+            elif mask != "none":
+                geom.update(bias=table.data_ptr() if table is not None else 0, bias_heads=hb,
+                            Sp=Sp if table is not None else 0, causal=int(mask == "causal"))
+            geom = native.geometry(geom)
+
             def launch():
-                st = torch.cuda.current_stream().cuda_stream
-                if mask == "keypad":
-                    rc = L.die_kern_attention_keymask(base, base + 2 * C, base + 4 * C, out.data_ptr(), B, S, H, D,
-                                                      3 * C, 3 * C, 3 * C, C, float(1 / np.sqrt(D)), st, int(split), 0, 0,
-                                                      Sp, 0, kvis.data_ptr(), kend.data_ptr())
-                elif mask == "none":
-                    rc = L.die_kern_attention(base, base + 2 * C, base + 4 * C, out.data_ptr(), B, S, H, D, 3 * C,
-                                              3 * C, 3 * C, C, float(1 / np.sqrt(D)), st, int(split))
-                else:
-                    rc = L.die_kern_attention_masked(base, base + 2 * C, base + 4 * C, out.data_ptr(), B, S, H, D,
-                                                     3 * C, 3 * C, 3 * C, C, float(1 / np.sqrt(D)), st, int(split),
-                                                     table.data_ptr() if table is not None else 0, hb,
-                                                     Sp if table is not None else 0, int(mask == "causal"))
+                rc = L.die_kern_attention(geom, torch.cuda.current_stream().cuda_stream)
                 assert rc == 0, rc
 
             first = None

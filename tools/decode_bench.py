@@ -60,13 +60,9 @@ def main():
                 d_poffs = torch.arange(B, dtype=torch.int64, device="cuda") * (cap // 2)
 
             def run(packed=False):
-                if packed:
-                    rc = L.die_kern_decode_packed(d_text.data_ptr(), 0, d_packed.data_ptr(), d_poffs.data_ptr(), cap,
-                                                  d_lens.data_ptr(), B, out.data_ptr(), numel, st.data_ptr(),
-                                                  st.data_ptr() + 4 * B, scratch.data_ptr(), s)
-                else:
-                    rc = L.die_kern_decode(d_text.data_ptr(), 0, cap, d_lens.data_ptr(), B, out.data_ptr(), numel,
-                                           st.data_ptr(), st.data_ptr() + 4 * B, scratch.data_ptr(), s)
+                rc = L.die_kern_decode(d_text.data_ptr(), 0, d_packed.data_ptr() if packed else 0,
+                                       d_poffs.data_ptr() if packed else 0, cap, d_lens.data_ptr(), B, out.data_ptr(), numel,
+                                       st.data_ptr(), st.data_ptr() + 4 * B, scratch.data_ptr(), s)
                 assert rc == 0
 
             for packed in (((True,) if args.packed_only else (False, True)) if packed_ok else (False,)):

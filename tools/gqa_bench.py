@@ -91,10 +91,12 @@ def kernel_section(lines, results):
                     out = torch.empty(((2,) if split else ()) + (B, S, C), dtype=torch.bfloat16, device="cuda")
                     base = int(xin.data_ptr())
 
+                    geom = native.geometry(dict(q=base, k=base + 2 * C, v=base + 2 * (C + kw), out=int(out.data_ptr()), B=B, S=S,
+                                                H=H, D=D, ldq=ld, ldk=ld, ldv=ld, ldo=C, scale=scale, split=split,
+                                                causal=causal, kv_heads=Hkv if gqa else H))
+
                     def attn():
-                        rc = L.die_kern_attention_gqa(base, base + 2 * C, base + 2 * (C + kw), int(out.data_ptr()), B, S, H, D,
-                                                      ld, ld, ld, C, scale, st(), split, 0, 0, 0, causal, 0, 0,
-                                                      Hkv if gqa else H)
+                        rc = L.die_kern_attention(geom, st())
                         assert rc == 0, rc
 
                     attn()

@@ -70,7 +70,8 @@ def main():
             plane_bytes = 2 * (2 if split else 1)
 
             def gap():
-                rc = L.die_kern_gap(int(xin.data_ptr()), int(out.data_ptr()), int(out32.data_ptr()), 0, 0, 0, B, S, D, st(), int(split))
+                rc = L.die_kern_gap(int(xin.data_ptr()), int(out.data_ptr()), int(out32.data_ptr()), 0, 0, 0, B, S, D, st(), int(split),
+                                    0, 0)
                 assert rc == 0, rc
 
             gap()
@@ -87,11 +88,14 @@ def main():
                     vis[:, :n] = True
                     kvis, kend = K.key_mask_data(vis)
 
+                    geom = native.geometry(dict(x=int(xin.data_ptr()), out=int(out.data_ptr()), out_f32=int(out32.data_ptr()), B=B,
+                                                S=S, C=D, D=D, kvis=int(kvis.data_ptr()), kend=int(kend.data_ptr()),
+                                                Sp=int(kvis.shape[1]), clip_min=1e-9, normalize=normalize, eps=1e-12,
+                                                split=int(split), ws=int(ws.data_ptr()), ws_bytes=ws_bytes,
+                                                counters=int(counters.data_ptr()), counters_n=B))
+
                     def pool():
-                        rc = L.die_kern_pool_tokens(int(xin.data_ptr()), int(out.data_ptr()), int(out32.data_ptr()), B, S, D, D,
-                                                    int(kvis.data_ptr()), int(kend.data_ptr()), int(kvis.shape[1]), 1e-9,
-                                                    normalize, 1e-12, st(), 0, int(split), int(ws.data_ptr()), ws_bytes,
-                                                    int(counters.data_ptr()), B)
+                        rc = L.die_kern_pool_tokens(geom, st())
                         assert rc == 0, rc
 
                     pool()

@@ -92,8 +92,8 @@ def main():
             y = torch.empty(((2,) if split else ()) + (rows, C), dtype=torch.bfloat16, device="cuda")
             for rms in (1, 0):  # the LayerNorm mode of the same kernel at the same shape beside it
                 def norm():
-                    rc = L.die_kern_layernorm_ex(int(xin.data_ptr()), int(y.data_ptr()), int(g.data_ptr()), int(g.data_ptr()), 1e-6,
-                                                 rows, C, st(), int(split), 0, 0, 0, rms)
+                    rc = L.die_kern_layernorm(int(xin.data_ptr()), int(y.data_ptr()), int(g.data_ptr()), int(g.data_ptr()), 1e-6,
+                                              rows, C, st(), int(split), 0, 0, 0, rms)
                     assert rc == 0, rc
 
                 norm()
