@@ -501,6 +501,31 @@ int die_kern_dwconv(const char* geom, int tiled, uint64_t x, uint64_t w, uint64_
   }
 }
 
+// GroupNorm / InstanceNorm (kern::group_norm): geom's keys are the scalar members of GroupNormArgs.
+// Returns the hipError_t (1 = hipErrorInvalidValue: bad arguments, nothing launched).
+long long die_groupnorm_workspace_bytes(int B, int HW, int C, int G) {
+  return static_cast<long long>(kern::group_norm_workspace_bytes(B, HW, C, G));
+}
+int die_kern_groupnorm(const char* geom, uint64_t x, uint64_t gamma, uint64_t beta, uint64_t out, uint64_t ws,
+                       uint64_t live, uint64_t stream) {
+  try {
+    kern::GroupNormArgs a;
+    Geom g(geom);
+    g("B", a.B), g("HW", a.HW), g("C", a.C), g("Cl", a.Cl), g("G", a.G), g("eps", a.eps), g("act", a.act);
+    g("split", a.split), g("ws_bytes", a.ws_bytes);
+    g.done();
+    a.x = P<const uint16_t>(x);
+    a.gamma = P<const float>(gamma);
+    a.beta = P<const float>(beta);
+    a.out = P<uint16_t>(out);
+    a.ws = P<float>(ws);
+    a.live = P<const long long>(live);
+    return static_cast<int>(kern::group_norm(a, S(stream)));
+  } catch (...) {
+    return -1;
+  }
+}
+
 int die_kern_softmax(uint64_t x, uint64_t y, uint64_t yf, long long rows, int C, uint64_t stream, int split) {
   return static_cast<int>(kern::softmax_rows(P<const uint16_t>(x), P<uint16_t>(y), P<float>(yf), rows, C, S(stream), split));
 }
@@ -715,6 +740,14 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
         e["ld_in"] = o.ld[0];
         e["col"] = o.col[0];
         e["layout"] = o.gidx ? "nshd" : "nhsd";  // the logical head view the rotation was written on
+      }
+      if (o.kind == PlanOp::GROUPNORM) {
+        e["groups"] = o.groups;  // == channels: InstanceNorm
+        e["channels"] = o.Cp;
+        e["stored_channels"] = o.C;
+        e["pixels"] = o.H * o.W;
+        e["act"] = o.act;  // 0 none, 1 ReLU, 2 SiLU
+        e["eps"] = static_cast<double>(o.eps);
       }
       if (o.kind == PlanOp::CONV || o.kind == PlanOp::TOKENS) e["stats_out"] = o.out_stats >= 0;  // writes the partials
       if (o.kind == PlanOp::STEM) {

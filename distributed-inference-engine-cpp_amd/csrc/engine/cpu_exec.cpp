@@ -655,6 +655,45 @@ CpuValuePtr op_rmsnorm(const Node& n, const CpuValue& x, const CpuValue* scale, 
   return y;
 }
 
+// InstanceNormalization (any rank >= 3: torch's GroupNorm export feeds it [N, G, Cg*H*W]) and
+// GroupNormalization, x = [N, C, spatial...]: y = (x - mean) / sqrt(var + eps) * scale + bias with the
+// biased variance over each (sample, group)'s C / G channels times the spatial elements, in fp64.
+// groups == 0: InstanceNormalization (a group per channel).  scale / bias are per channel [C] or
+// (GroupNormalization of opset 18) per group [G]; told apart by their length -- with G == C the two
+// mean the same.
+CpuValuePtr op_group_norm(const Node& n, const CpuValue& x, const CpuValue& scale, const CpuValue& bias, int64_t groups) {
+  const size_t r = x.shape.size();
+  if (r < 3 || x.is_int) fail(n, "needs a float input of rank >= 3");
+  const int64_t N = x.shape[0], C = x.shape[1], G = groups > 0 ? groups : C;
+  if (C < 1 || C % G) fail(n, "num_groups must divide the channels");
+  const int64_t Cg = C / G;
+  int64_t sp = 1;
+  for (size_t k = 2; k < r; ++k) sp *= x.shape[k];
+  const int64_t ns = static_cast<int64_t>(scale.f.size()), nb = static_cast<int64_t>(bias.f.size());
+  if ((ns != C && ns != G) || (nb != C && nb != G) || scale.is_int || bias.is_int)
+    fail(n, "scale / bias must hold one float per channel or per group");
+  const double eps = n.get_float("epsilon", 1e-5f);
+  auto y = make_f(x.shape);
+  const int64_t D = Cg * sp;
+#pragma omp parallel for if (N * G > 16)
+  for (int64_t o = 0; o < N * G; ++o) {
+    const float* in = x.f.data() + o * D;
+    float* out = y->f.data() + o * D;
+    double mean = 0, var = 0;
+    for (int64_t d = 0; d < D; ++d) mean += in[d];
+    mean /= static_cast<double>(D);
+    for (int64_t d = 0; d < D; ++d) var += (in[d] - mean) * (in[d] - mean);
+    var /= static_cast<double>(D);
+    const double inv = 1.0 / std::sqrt(var + eps);
+    const int64_t g = o % G;
+    for (int64_t c = 0; c < Cg; ++c) {
+      const double s = scale.f[ns == C ? g * Cg + c : g], b = bias.f[nb == C ? g * Cg + c : g];
+      for (int64_t d = c * sp; d < (c + 1) * sp; ++d) out[d] = static_cast<float>((in[d] - mean) * inv * s + b);
+    }
+  }
+  return y;
+}
+
 CpuValuePtr op_reduce(const Node& n, const std::vector<const CpuValue*>& in, int64_t opset) {
   const CpuValue& x = *in[0];
   const size_t r = x.shape.size();
@@ -1193,6 +1232,11 @@ CpuValuePtr CpuExecutor::run(const CpuValuePtr& input, std::unordered_map<std::s
       out = op_softmax(n, *in[0], opset);
     } else if (op == "LayerNormalization") {
       out = op_layernorm(n, *in[0], in.size() > 1 ? in[1] : nullptr, in.size() > 2 ? in[2] : nullptr);
+    } else if (op == "InstanceNormalization" || op == "GroupNormalization") {
+      if (in.size() < 3 || !in[0] || !in[1] || !in[2]) fail(n, "needs x, scale and bias");
+      const int64_t groups = op == "GroupNormalization" ? n.get_int("num_groups", 0) : 0;
+      if (op == "GroupNormalization" && groups < 1) fail(n, "needs num_groups >= 1");
+      out = op_group_norm(n, *in[0], *in[1], *in[2], groups);
     } else if (op == "RMSNormalization" || op == "SimplifiedLayerNormalization") {
       if (in[0]->is_int) fail(n, "needs a float input");
       CpuValuePtr inv_std;

@@ -334,6 +334,26 @@ hipError_t HipEngine::launch_op(const PlanOp& op, size_t op_index, int B, int s,
       e = kern::rope_rows(cbf(op.in) + op.col[0], bf(op.out), prm(op.scale_off), prm(op.shift_off), B, op.S, op.nh,
                           op.hd, op.ld[0], op.C, st, sp_);
       break;
+    case PlanOp::GROUPNORM: {
+      kern::GroupNormArgs g;
+      g.x = cbf(op.in);
+      g.out = bf(op.out);
+      g.gamma = prm(op.scale_off);
+      g.beta = prm(op.shift_off);
+      g.B = B;
+      g.HW = op.H * op.W;
+      g.C = op.C;
+      g.Cl = op.Cp;
+      g.G = op.groups;
+      g.eps = op.eps;
+      g.act = op.act;
+      g.split = sp_;
+      g.live = live;
+      g.ws = f32(op.out2);  // a plan buffer of the arena: kern::group_norm_workspace_bytes per sample
+      g.ws_bytes = kern::group_norm_workspace_bytes(B, g.HW, g.C, g.G);
+      e = kern::group_norm(g, st);
+      break;
+    }
     case PlanOp::GCONV: {
       kern::GConvArgs g;
       g.x = cbf(op.in);
@@ -432,6 +452,12 @@ Json HipEngine::profile_ops(int B, int iters) {
       o["normalize"] = op.normalize;
     }
     if (op.kind == PlanOp::LAYERNORM) o["rms"] = op.rms != 0;
+    if (op.kind == PlanOp::GROUPNORM) {
+      o["groups"] = op.groups;
+      o["channels"] = op.Cp;
+      o["pixels"] = op.H * op.W;
+      o["act"] = op.act;
+    }
     total += us[i];
     ops.push_back(o);
   }

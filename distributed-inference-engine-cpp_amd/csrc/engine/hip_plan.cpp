@@ -226,7 +226,12 @@ bool Planner::reports_own_input(const Node& n) const {
   // says that the table must be an initializer)
   if (n.op_type == "Gather" && token_node(n)) return true;
   // (and the Mul of a heads view by a rotary table that came from one: the tables must be initializers)
-  return n.op_type == "Mul" && rope_anchor(n);
+  if (n.op_type == "Mul" && rope_anchor(n)) return true;
+  // (and a GroupNormalization / InstanceNormalization of a known value whose scale or bias came from
+  // one: they must be initializers)
+  if (n.op_type != "GroupNormalization" && n.op_type != "InstanceNormalization") return false;
+  auto it = vid_.find(n.in(0));
+  return it != vid_.end() && vals_[it->second].kind != Val::UNKNOWN;
 }
 
 // The dispatch.  Its order is semantics, not style: the predicates on the operands' kinds come before
@@ -234,7 +239,8 @@ bool Planner::reports_own_input(const Node& n) const {
 // node with a token-id / key-mask operand (token_node) before a repeat_kv in progress
 // (kv_repeat_node), then the shape subgraph (lower_shape_op), then the anchors of the multi-node
 // RoPE and RMSNorm patterns (which take Mul / Slice / Pow nodes away from lower_scale, lower_slice
-// and lower_unary), and only then one line per op type.
+// and lower_unary) and of torch's GroupNorm export (a Reshape of an image read by an
+// InstanceNormalization, taken away from lower_reshape), and only then one line per op type.
 void Planner::lower(int idx) {
   const Node& n = m_.nodes[idx];
   const std::string& op = n.op_type;
@@ -244,6 +250,8 @@ void Planner::lower(int idx) {
   if ((op == "Mul" || op == "Slice") && rope_anchor(n)) return lower_rope(idx);
   if ((op == "Pow" || (op == "Mul" && n.inputs.size() == 2 && n.in(0) == n.in(1))) && rmsnorm_anchor(n)) return lower_rmsnorm(idx);
   if (op == "RMSNormalization" || op == "SimplifiedLayerNormalization") return lower_layernorm(idx);
+  if (op == "Reshape" && groupnorm_anchor(n)) return lower_groupnorm_chain(idx);
+  if (op == "InstanceNormalization" || op == "GroupNormalization") return lower_groupnorm(idx);
   if (op == "Conv") return n.get_int("group", 1) != 1 ? lower_gconv(idx) : lower_conv(idx);
   if (op == "Gemm" || (op == "MatMul" && is_init(n.in(1)))) return lower_gemm(idx);
   if (op == "MatMul") return lower_attn_matmul(idx);
@@ -358,8 +366,8 @@ const char* plan_kind_name(PlanOp::Kind kind) {
   static const char* kinds[] = {"input_prep", "conv", "pool", "gap", "affine", "to_nchw_f32", "bf16_to_f32",
                                 "layernorm", "tokens", "gather_rows", "attention", "stem", "gconv", "softmax",
                                 "rows_prep", "copy_cols", "binary", "unary", "conv_pair", "pad", "where", "resize", "bmm", "gap_fc",
-                                "embed_tokens", "pool_tokens", "rope"};
-  static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::ROPE + 1, "one name per PlanOp kind");
+                                "embed_tokens", "pool_tokens", "rope", "groupnorm"};
+  static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::GROUPNORM + 1, "one name per PlanOp kind");
   return kinds[kind];
 }
 

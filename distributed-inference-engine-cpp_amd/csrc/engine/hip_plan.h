@@ -11,6 +11,8 @@
 //  * plan_lower_tokens.cpp    token-id models, attention_mask / token_type_ids inputs, sentence pooling,
 //                             ViT token assembly
 //  * plan_lower_norm.cpp      LayerNormalization, RMSNorm and their decomposed exports
+//  * plan_lower_groupnorm.cpp InstanceNormalization, GroupNormalization and torch's Reshape / InstanceNorm /
+//                             Reshape export of GroupNorm, with a trailing ReLU / SiLU
 //  * plan_lower_general.cpp   everything else: standalone unary / binary / compare / Where / concat / slice
 // Anything the planner cannot lower is rejected with a clear error (the CPU executor still runs such
 // models).
@@ -79,9 +81,13 @@ struct PlanOp {
                  // graph output).  key_mask = 1: the mean over the visible tokens, sum / max(count, count_min),
                  // with in4 / in5 = the EMBED_TOKENS op's kvis / kend; else the mean of all S rows.
                  // normalize: then v / max(||v||_2, eps).  S = 1, normalize: a row L2 normalisation
-    ROPE  // rotary position embedding (rotate-half) of the nh heads of hd columns at in [S][ld[0]] + col[0] ->
-          // dense rows out [S][nh*hd]; scale_off / shift_off = the cos / sin tables [S][hd] f32
-          // (kern::rope_rows); gidx = the layout the graph rotated in (0: [N, H, S, hd], 1: [N, S, H, hd])
+    ROPE,  // rotary position embedding (rotate-half) of the nh heads of hd columns at in [S][ld[0]] + col[0] ->
+           // dense rows out [S][nh*hd]; scale_off / shift_off = the cos / sin tables [S][hd] f32
+           // (kern::rope_rows); gidx = the layout the graph rotated in (0: [N, H, S, hd], 1: [N, S, H, hd])
+    GROUPNORM  // GroupNorm / InstanceNorm of the image in [H][W][C] (Cp logical channels) over `groups` groups
+               // (groups = Cp: InstanceNorm): out = act((in - mean) * rstd * gamma + beta), scale_off /
+               // shift_off = gamma / beta [Cp] f32 (SIZE_MAX: none), act 0 none, 1 ReLU, 2 SiLU, eps;
+               // out2 = the launch's workspace (kern::group_norm_workspace_bytes per sample)
   } kind;
   std::string name;
   // buffers (-1 = none).  -2 = the graph input (f32 NCHW), -3 = the graph output (f32).

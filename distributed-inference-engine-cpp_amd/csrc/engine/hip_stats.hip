@@ -77,6 +77,21 @@ Json HipEngine::stats() const {
       }
     j["attention"] = at;
   }
+  {  // the GroupNorm / InstanceNorm ops' geometry (groups == channels: InstanceNorm); act 0 none, 1 ReLU, 2 SiLU
+    Json gn = Json::array();
+    for (const PlanOp& op : plan_.ops)
+      if (op.kind == PlanOp::GROUPNORM) {
+        Json o = Json::object();
+        o["name"] = op.name;
+        o["groups"] = op.groups;
+        o["channels"] = op.Cp;
+        o["stored_channels"] = op.C;
+        o["pixels"] = op.H * op.W;
+        o["act"] = op.act;
+        gn.push_back(o);
+      }
+    if (gn.size()) j["groupnorm"] = gn;
+  }
   j["inputs"] = input_segments_json(plan_.inputs);  // the graph inputs as segments of a request
   j["precision"] = sp_ ? "fp32" : "bf16";
   j["gflop_per_image"] = plan_.flops_per_sample / 1e9;

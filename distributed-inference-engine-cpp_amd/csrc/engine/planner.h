@@ -299,6 +299,13 @@ class Planner {
   static int64_t last_axis_of(const Node& n, const onnx::Model& m, bool& ok);
   void lower_reduce_mean(int idx);
 
+  // ---- plan_lower_groupnorm.cpp ----
+  bool groupnorm_anchor(const Node& n) const;
+  void lower_groupnorm_chain(int idx);
+  void lower_groupnorm(int idx);
+  void emit_groupnorm(const Node& n, const std::string& name, const Val& x, int G, std::vector<float> gamma,
+                      std::vector<float> beta, float eps, std::string cur);
+
   // ---- plan_lower_general.cpp ----
   bool scalar_init(const std::string& name, float& v) const;
   void lower_compare(int idx);

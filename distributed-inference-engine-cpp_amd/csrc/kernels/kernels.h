@@ -183,6 +183,34 @@ hipError_t grouped_conv(const GConvArgs& a, hipStream_t s);
 bool dwconv_tiled_supported(const GConvArgs& a);
 hipError_t dwconv_tiled(const GConvArgs& a, hipStream_t s);
 
+// GroupNorm / InstanceNorm of an NHWC image x [B][HW][C] (groupnorm.hip), per (sample, group):
+//   y = act((x - mean[b, g]) * rsqrt(var[b, g] + eps) * gamma[c] + beta[c])
+// over the G groups of Cg = Cl / G consecutive logical channels (any Cg >= 1; G = Cl: InstanceNorm),
+// biased variance over the HW * Cg elements, fp32 (count, mean, M2) statistics merged in a fixed order
+// that depends on (HW, C, G) only -- no atomics, the same bits for a sample whatever B, its place in
+// the batch or *live.  Stored pad channels [Cl, C) are written 0.  out may be x (in place).
+// Capturable: partials and the per-group (mean, rstd) go through `ws`, at least
+// group_norm_workspace_bytes(B, HW, C, G) bytes, 8-byte aligned, not shared with a launch that may run
+// at the same time.  Cl % G != 0, C % 8 != 0 or C > 2048, x / out not 16-byte aligned, gamma / beta / ws
+// misaligned, an unknown act, a missing or too-small workspace: hipErrorInvalidValue, nothing launched.
+struct GroupNormArgs {
+  const uint16_t* x = nullptr;
+  uint16_t* out = nullptr;
+  const float* gamma = nullptr;  // [Cl], nullable (1)
+  const float* beta = nullptr;   // [Cl], nullable (0)
+  int B = 1, HW = 1, C = 8;
+  int Cl = 0;                    // logical channels (0 = C)
+  int G = 1;
+  float eps = 1e-5f;
+  int act = 0;                   // 0 none, 1 ReLU, 2 SiLU (y * sigmoid(y))
+  int split = 0;
+  const long long* live = nullptr;
+  float* ws = nullptr;
+  size_t ws_bytes = 0;
+};
+size_t group_norm_workspace_bytes(int B, int HW, int C, int G);
+hipError_t group_norm(const GroupNormArgs& a, hipStream_t s);
+
 // Softmax over the last axis of [rows][C] (one wave per row, fp32 math); writes bf16/split `y`
 // (row pitch ld) and/or f32 `y_f32` (dense [rows][C]).  ld = stored row pitch of x and y (0 = C).
 hipError_t softmax_rows(const uint16_t* x, uint16_t* y, float* y_f32, long long rows, int C, hipStream_t s,

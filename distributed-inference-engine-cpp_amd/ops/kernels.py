@@ -865,6 +865,42 @@ def depthwise_conv(x_nhwc, w, bias=None, pads=(0, 0, 0, 0), stride=1, dilation=1
     return out, of
 
 
+GN_ACTS = {None: 0, "none": 0, "relu": 1, "silu": 2}
+
+
+def group_norm(x_nhwc, G, gamma=None, beta=None, eps=1e-5, act=None, split=False, live=None, fill=None, Cl=None,
+               ws_bytes=None, out=None):
+    """GroupNorm / InstanceNorm (csrc/kernels/groupnorm.hip) of x [B,H,W,C] (bf16, or any float dtype with
+    split) over G groups of the first Cl (default C) channels; gamma / beta [Cl] float or None; act None,
+    "relu" or "silu".  live: number of leading samples to compute (a device-side count; the others keep
+    `fill`).  ws_bytes: the workspace size to allocate and declare (default: what the launcher asks for).
+    out: a caller's buffer of the stored shape to write into (an error leaves it as it was).
+    Returns the stored planes: bf16 [B,H,W,C], or [2,B,H,W,C] hi / lo when split.  Bad arguments raise
+    NativeError with hipError 1 and launch nothing."""
+    import torch
+
+    B, H, W, C = x_nhwc.shape
+    dev = x_nhwc.device
+    xin = _in(x_nhwc, split) if split else x_nhwc.to(torch.bfloat16).contiguous()
+    gp = None if gamma is None else gamma.float().contiguous()
+    bp = None if beta is None else beta.float().contiguous()
+    if out is None:
+        out = torch.empty(((2,) if split else ()) + (B, H, W, C), dtype=torch.bfloat16, device=dev)
+    assert out.shape == ((2,) if split else ()) + (B, H, W, C) and out.dtype == torch.bfloat16 and out.is_contiguous()
+    if fill is not None:
+        out.fill_(fill)
+    need = int(native.kernels().die_groupnorm_workspace_bytes(B, H * W, C, int(G)))
+    nbytes = need if ws_bytes is None else int(ws_bytes)
+    ws = torch.empty((max(nbytes, 8) + 3) // 4, dtype=torch.float32, device=dev)
+    lv = None if live is None else torch.tensor([int(live)], dtype=torch.int64, device=dev)
+    geom = dict(B=B, HW=H * W, C=C, Cl=C if Cl is None else int(Cl), G=int(G), eps=float(eps), act=GN_ACTS[act],
+                split=int(split), ws_bytes=nbytes)
+    rc = native.kernels().die_kern_groupnorm(json.dumps(geom).encode(), _ptr(xin), _ptr(gp), _ptr(bp), _ptr(out),
+                                             _ptr(ws), _ptr(lv), _stream())
+    _check(rc, "group_norm")
+    return out
+
+
 def softmax_rows(x, split=False):
     """x [rows, C] float -> (softmax stored bf16/split -> fp32 values, softmax fp32)."""
     import torch
