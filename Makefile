@@ -20,7 +20,7 @@ HOST_SRCS := core/json.cpp core/http.cpp core/http_async.cpp core/log.cpp core/m
              serve/worker.cpp serve/gateway.cpp serve/loadgen.cpp onnx/onnx_model.cpp \
              engine/engine.cpp engine/cpu_exec.cpp engine/hybrid_engine.cpp engine/hip_plan.cpp engine/plan_passes.cpp \
              engine/plan_lower_image.cpp engine/plan_lower_gemm.cpp engine/plan_lower_attention.cpp \
-             engine/plan_lower_tokens.cpp engine/plan_lower_norm.cpp engine/plan_lower_groupnorm.cpp engine/plan_lower_general.cpp engine/tune_cache.cpp capi/capi.cpp capi/capi_kernels.cpp
+             engine/plan_lower_tokens.cpp engine/plan_lower_norm.cpp engine/plan_lower_groupnorm.cpp engine/plan_lower_grn.cpp engine/plan_lower_general.cpp engine/tune_cache.cpp capi/capi.cpp capi/capi_kernels.cpp
 HIP_SRCS  := $(notdir $(wildcard $(SRC)/engine/*.hip)) $(notdir $(wildcard $(SRC)/kernels/*.hip))
 HOST_OBJS := $(addprefix $(BUILD)/host/,$(HOST_SRCS:.cpp=.o))
 HIP_OBJS  := $(patsubst %.hip,$(BUILD)/hip/%.o,$(HIP_SRCS))

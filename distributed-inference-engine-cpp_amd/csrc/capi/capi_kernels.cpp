@@ -526,6 +526,30 @@ int die_kern_groupnorm(const char* geom, uint64_t x, uint64_t gamma, uint64_t be
   }
 }
 
+// Global Response Normalization (kern::grn): geom's keys are the scalar members of GrnArgs.
+// Returns the hipError_t (1 = hipErrorInvalidValue: bad arguments, nothing launched).
+long long die_grn_workspace_bytes(int B, int HW, int C) {
+  return static_cast<long long>(kern::grn_workspace_bytes(B, HW, C));
+}
+int die_kern_grn(const char* geom, uint64_t x, uint64_t gamma, uint64_t beta, uint64_t out, uint64_t ws, uint64_t live,
+                 uint64_t stream) {
+  try {
+    kern::GrnArgs a;
+    Geom g(geom);
+    g("B", a.B), g("HW", a.HW), g("C", a.C), g("eps", a.eps), g("split", a.split), g("ws_bytes", a.ws_bytes), g("form", a.form);
+    g.done();
+    a.x = P<const uint16_t>(x);
+    a.gamma = P<const float>(gamma);
+    a.beta = P<const float>(beta);
+    a.out = P<uint16_t>(out);
+    a.ws = P<float>(ws);
+    a.live = P<const long long>(live);
+    return static_cast<int>(kern::grn(a, S(stream)));
+  } catch (...) {
+    return -1;
+  }
+}
+
 int die_kern_softmax(uint64_t x, uint64_t y, uint64_t yf, long long rows, int C, uint64_t stream, int split) {
   return static_cast<int>(kern::softmax_rows(P<const uint16_t>(x), P<uint16_t>(y), P<float>(yf), rows, C, S(stream), split));
 }
@@ -748,6 +772,13 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
         e["pixels"] = o.H * o.W;
         e["act"] = o.act;  // 0 none, 1 ReLU, 2 SiLU
         e["eps"] = static_cast<double>(o.eps);
+      }
+      if (o.kind == PlanOp::GRN) {
+        e["C"] = o.C;
+        e["rows"] = o.H * o.W;  // pixels of the map
+        e["eps"] = static_cast<double>(o.eps);
+        e["gamma"] = o.scale_off != SIZE_MAX;
+        e["beta"] = o.shift_off != SIZE_MAX;
       }
       if (o.kind == PlanOp::CONV || o.kind == PlanOp::TOKENS) e["stats_out"] = o.out_stats >= 0;  // writes the partials
       if (o.kind == PlanOp::STEM) {

@@ -354,6 +354,23 @@ hipError_t HipEngine::launch_op(const PlanOp& op, size_t op_index, int B, int s,
       e = kern::group_norm(g, st);
       break;
     }
+    case PlanOp::GRN: {
+      kern::GrnArgs g;
+      g.x = cbf(op.in);
+      g.out = bf(op.out);
+      g.gamma = prm(op.scale_off);
+      g.beta = prm(op.shift_off);
+      g.B = B;
+      g.HW = op.H * op.W;
+      g.C = op.C;
+      g.eps = op.eps;
+      g.split = sp_;
+      g.live = live;
+      g.ws = f32(op.out2);  // a plan buffer of the arena: kern::grn_workspace_bytes per sample
+      g.ws_bytes = kern::grn_workspace_bytes(B, g.HW, g.C);
+      e = kern::grn(g, st);
+      break;
+    }
     case PlanOp::GCONV: {
       kern::GConvArgs g;
       g.x = cbf(op.in);
@@ -457,6 +474,11 @@ Json HipEngine::profile_ops(int B, int iters) {
       o["channels"] = op.Cp;
       o["pixels"] = op.H * op.W;
       o["act"] = op.act;
+    }
+    if (op.kind == PlanOp::GRN) {
+      o["C"] = op.C;
+      o["rows"] = op.H * op.W;
+      o["eps"] = static_cast<double>(op.eps);
     }
     total += us[i];
     ops.push_back(o);

@@ -366,8 +366,8 @@ const char* plan_kind_name(PlanOp::Kind kind) {
   static const char* kinds[] = {"input_prep", "conv", "pool", "gap", "affine", "to_nchw_f32", "bf16_to_f32",
                                 "layernorm", "tokens", "gather_rows", "attention", "stem", "gconv", "softmax",
                                 "rows_prep", "copy_cols", "binary", "unary", "conv_pair", "pad", "where", "resize", "bmm", "gap_fc",
-                                "embed_tokens", "pool_tokens", "rope", "groupnorm"};
-  static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::GROUPNORM + 1, "one name per PlanOp kind");
+                                "embed_tokens", "pool_tokens", "rope", "groupnorm", "grn"};
+  static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::GRN + 1, "one name per PlanOp kind");
   return kinds[kind];
 }
 

@@ -13,6 +13,8 @@
 //  * plan_lower_norm.cpp      LayerNormalization, RMSNorm and their decomposed exports
 //  * plan_lower_groupnorm.cpp InstanceNormalization, GroupNormalization and torch's Reshape / InstanceNorm /
 //                             Reshape export of GroupNorm, with a trailing ReLU / SiLU
+//  * plan_lower_grn.cpp       ConvNeXt-V2's Global Response Normalization: the ReduceL2(two spatial axes) /
+//                             ReduceMean / Add / Div / Mul / Mul / Add / Add chain, channels-last or -first
 //  * plan_lower_general.cpp   everything else: standalone unary / binary / compare / Where / concat / slice
 // Anything the planner cannot lower is rejected with a clear error (the CPU executor still runs such
 // models).
@@ -84,10 +86,14 @@ struct PlanOp {
     ROPE,  // rotary position embedding (rotate-half) of the nh heads of hd columns at in [S][ld[0]] + col[0] ->
            // dense rows out [S][nh*hd]; scale_off / shift_off = the cos / sin tables [S][hd] f32
            // (kern::rope_rows); gidx = the layout the graph rotated in (0: [N, H, S, hd], 1: [N, S, H, hd])
-    GROUPNORM  // GroupNorm / InstanceNorm of the image in [H][W][C] (Cp logical channels) over `groups` groups
-               // (groups = Cp: InstanceNorm): out = act((in - mean) * rstd * gamma + beta), scale_off /
-               // shift_off = gamma / beta [Cp] f32 (SIZE_MAX: none), act 0 none, 1 ReLU, 2 SiLU, eps;
-               // out2 = the launch's workspace (kern::group_norm_workspace_bytes per sample)
+    GROUPNORM,  // GroupNorm / InstanceNorm of the image in [H][W][C] (Cp logical channels) over `groups` groups
+                // (groups = Cp: InstanceNorm): out = act((in - mean) * rstd * gamma + beta), scale_off /
+                // shift_off = gamma / beta [Cp] f32 (SIZE_MAX: none), act 0 none, 1 ReLU, 2 SiLU, eps;
+                // out2 = the launch's workspace (kern::group_norm_workspace_bytes per sample)
+    GRN  // Global Response Normalization of the map in [H * W][C] (dense, no pad channels; an image or an
+         // [N, H, W, C] rows view of one): out = gamma * (in * nx) + beta + in with nx = G / (mean_c G + eps),
+         // G[c] = the L2 norm of channel c over the map; scale_off / shift_off = gamma / beta [C] f32
+         // (SIZE_MAX: none); out2 = the launch's workspace (kern::grn_workspace_bytes per sample)
   } kind;
   std::string name;
   // buffers (-1 = none).  -2 = the graph input (f32 NCHW), -3 = the graph output (f32).

@@ -92,6 +92,19 @@ Json HipEngine::stats() const {
       }
     if (gn.size()) j["groupnorm"] = gn;
   }
+  {  // the Global Response Normalization ops' geometry (rows = the pixels of the map)
+    Json gr = Json::array();
+    for (const PlanOp& op : plan_.ops)
+      if (op.kind == PlanOp::GRN) {
+        Json o = Json::object();
+        o["name"] = op.name;
+        o["C"] = op.C;
+        o["rows"] = op.H * op.W;
+        o["eps"] = static_cast<double>(op.eps);
+        gr.push_back(o);
+      }
+    if (gr.size()) j["grn"] = gr;
+  }
   j["inputs"] = input_segments_json(plan_.inputs);  // the graph inputs as segments of a request
   j["precision"] = sp_ ? "fp32" : "bf16";
   j["gflop_per_image"] = plan_.flops_per_sample / 1e9;

@@ -581,6 +581,7 @@ bool Planner::only_l2_normalized(const std::string& x, float& eps, std::string& 
 // LpNormalization / ReduceL2 on rows that are not a pooled vector's only use: POOL_TOKENS with S = 1.
 void Planner::lower_l2norm(int idx) {
   const Node& n = m_.nodes[idx];
+  if (grn_anchor(n)) return lower_grn(idx);  // two axes of an image / an [N, H, W, C] view: ConvNeXt-V2's GRN
   const Val x = val(n.in(0), n);
   const int rank = x.rank ? x.rank : 2;
   float eps = 0.f;

@@ -306,6 +306,10 @@ class Planner {
   void emit_groupnorm(const Node& n, const std::string& name, const Val& x, int G, std::vector<float> gamma,
                       std::vector<float> beta, float eps, std::string cur);
 
+  // ---- plan_lower_grn.cpp ----
+  bool grn_anchor(const Node& n) const;
+  void lower_grn(int idx);
+
   // ---- plan_lower_general.cpp ----
   bool scalar_init(const std::string& name, float& v) const;
   void lower_compare(int idx);

@@ -211,6 +211,31 @@ struct GroupNormArgs {
 size_t group_norm_workspace_bytes(int B, int HW, int C, int G);
 hipError_t group_norm(const GroupNormArgs& a, hipStream_t s);
 
+// Global Response Normalization (ConvNeXt-V2) of an NHWC map x [B][HW][C] (grn.hip), per sample:
+//   G[c] = sqrt(sum over the HW pixels of x[p][c]^2),  nx[c] = G[c] / (mean over c of G + eps),
+//   y = gamma[c] * (x * nx[c]) + beta[c] + x   computed as   fma(x, 1 + gamma[c] * nx[c], beta[c])
+// Any C that is a multiple of 8 (the columns are tiled; no stored pad channels), fp32 sums merged in
+// fixed orders that depend on (HW, C) only -- no atomics, the same bits for a sample whatever B, its
+// place in the batch or *live.  out may be x (in place).  Capturable: partial sums and the per-sample
+// coefficients go through `ws`, at least grn_workspace_bytes(B, HW, C) bytes, 16-byte aligned, not shared
+// with a launch that may run at the same time.  C % 8 != 0, HW < 1, x / out / ws not 16-byte aligned,
+// gamma / beta misaligned, a missing or too-small workspace: hipErrorInvalidValue, nothing launched.
+struct GrnArgs {
+  const uint16_t* x = nullptr;
+  uint16_t* out = nullptr;
+  const float* gamma = nullptr;  // [C], nullable (0: y = x + beta)
+  const float* beta = nullptr;   // [C], nullable (0)
+  int B = 1, HW = 1, C = 8;
+  float eps = 1e-6f;
+  int split = 0;
+  const long long* live = nullptr;
+  float* ws = nullptr;
+  size_t ws_bytes = 0;
+  int form = 0;  // measurements only (tools/grn_bench.py): 1 = the one-launch form where C allows it, 2 = three launches
+};
+size_t grn_workspace_bytes(int B, int HW, int C);
+hipError_t grn(const GrnArgs& a, hipStream_t s);
+
 // Softmax over the last axis of [rows][C] (one wave per row, fp32 math); writes bf16/split `y`
 // (row pitch ld) and/or f32 `y_f32` (dense [rows][C]).  ld = stored row pitch of x and y (0 = C).
 hipError_t softmax_rows(const uint16_t* x, uint16_t* y, float* y_f32, long long rows, int C, hipStream_t s,

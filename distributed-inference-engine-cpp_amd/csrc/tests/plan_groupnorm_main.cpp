@@ -1,8 +1,8 @@
 // Stand-alone host program for the sanitizers (make plan-asan): the planner alone, no GPU code linked,
 // on ONNX files given on the command line (tools/plan_groupnorm_asan.sh writes the four models of
-// models/groupnorm.py and the rejected variants).  For each file and both precisions: the support
+// models/groupnorm.py and the rejected variants, tools/plan_convnextv2_asan.sh the two tiny ConvNeXt-V2 models).  For each file and both precisions: the support
 // report, and for a supported graph the plan's ops by kind.  Exits 1 when a file given after --supported
-// is not fully lowered or holds no groupnorm op.
+// is not fully lowered or holds neither a groupnorm nor a grn op.
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -15,7 +15,8 @@ using namespace die;
 
 // Stand-ins for the host helpers the planner asks the kernel library (HIP objects, not linked here):
 // the heuristic tile, "no" for the optional fusions, and the upper bound of the GroupNorm workspace
-// (256 statistics blocks per sample + the merged statistics, float2 per group).
+// (256 statistics blocks per sample + the merged statistics, float2 per group) and of the GRN one (64
+// blocks of partial sums per sample + the coefficients, a float per channel).
 namespace die {
 namespace kern {
 bool attention_supported(int, int, bool) { return true; }
@@ -26,6 +27,7 @@ bool stem_pool_supported(int, int, int, int, int, int, int) { return false; }
 size_t group_norm_workspace_bytes(int B, int HW, int C, int G) {
   return C % 8 || C > 2048 ? 0 : static_cast<size_t>(B) * 257 * G * 8;
 }
+size_t grn_workspace_bytes(int B, int HW, int C) { return C % 8 ? 0 : static_cast<size_t>(B) * 65 * C * 4; }
 }  // namespace kern
 }  // namespace die
 
@@ -50,7 +52,7 @@ int main(int argc, char** argv) {
       std::string line;
       for (const auto& kv : kinds) line += " " + kv.first + "=" + std::to_string(kv.second);
       std::printf("  %s;%s\n", p.summary().c_str(), line.c_str());
-      if (must_lower && !kinds.count("groupnorm")) ++bad;
+      if (must_lower && !kinds.count("groupnorm") && !kinds.count("grn")) ++bad;
     }
   }
   return bad ? 1 : 0;

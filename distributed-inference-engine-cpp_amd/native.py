@@ -764,6 +764,10 @@ def _sig_kernels():
     L.die_kern_groupnorm.argtypes = [C.c_char_p] + [u64] * 7
     L.die_groupnorm_workspace_bytes.restype = C.c_longlong
     L.die_groupnorm_workspace_bytes.argtypes = [i] * 4
+    L.die_kern_grn.restype = i  # (geometry, x, gamma, beta, out, ws, live, stream)
+    L.die_kern_grn.argtypes = [C.c_char_p] + [u64] * 7
+    L.die_grn_workspace_bytes.restype = C.c_longlong
+    L.die_grn_workspace_bytes.argtypes = [i] * 3
     L.die_kern_softmax.restype = i
     L.die_kern_softmax.argtypes = [u64, u64, u64, C.c_longlong, i, u64, i]
     L.die_kern_layernorm.restype = i

@@ -901,6 +901,43 @@ def group_norm(x_nhwc, G, gamma=None, beta=None, eps=1e-5, act=None, split=False
     return out
 
 
+def grn(x_nhwc, gamma=None, beta=None, eps=1e-6, split=False, live=None, fill=None, out=None, ws_bytes=None, form=0):
+    """Global Response Normalization (csrc/kernels/grn.hip) of x [B,H,W,C] (any float dtype; a contiguous bf16
+    tensor of the stored shape, [B,H,W,C] or split [2,B,H,W,C], is read where it is): y = gamma * (x * nx) + beta + x with nx = G / (mean_c G + eps), G[b,c] the L2 norm of channel c over
+    the map; gamma / beta [C] float or None (0).  live: number of leading samples to compute (a device-side
+    count; the others keep `fill`).  out: a caller's buffer of the stored shape to write into, which may be
+    the stored planes of x themselves (in place); an error leaves it as it was.  ws_bytes: the workspace size
+    to allocate and declare (default: what the launcher asks for); form: GrnArgs::form (measurements).
+    Returns the stored planes: bf16 [B,H,W,C], or [2,B,H,W,C] hi / lo when split.  Bad arguments raise
+    NativeError with hipError 1 and launch nothing."""
+    import torch
+
+    B, H, W, C = x_nhwc.shape[-4:]
+    dev = x_nhwc.device
+    stored = ((2,) if split else ()) + (B, H, W, C)
+    if x_nhwc.dtype == torch.bfloat16 and tuple(x_nhwc.shape) == stored and x_nhwc.is_contiguous():
+        xin = x_nhwc  # the stored planes themselves (bf16 [B,H,W,C], split: [2,B,H,W,C]): read in place, no copy
+    else:
+        assert x_nhwc.dim() == 4
+        xin = _in(x_nhwc, split) if split else x_nhwc.to(torch.bfloat16).contiguous()
+    gp = None if gamma is None else gamma.float().contiguous()
+    bp = None if beta is None else beta.float().contiguous()
+    if out is None:
+        out = torch.empty(stored, dtype=torch.bfloat16, device=dev)
+    assert tuple(out.shape) == stored and out.dtype == torch.bfloat16 and out.is_contiguous()
+    if fill is not None:
+        out.fill_(fill)
+    need = int(native.kernels().die_grn_workspace_bytes(B, H * W, C))
+    nbytes = need if ws_bytes is None else int(ws_bytes)
+    ws = torch.empty((max(nbytes, 16) + 3) // 4, dtype=torch.float32, device=dev)
+    lv = None if live is None else torch.tensor([int(live)], dtype=torch.int64, device=dev)
+    geom = dict(B=B, HW=H * W, C=C, eps=float(eps), split=int(split), ws_bytes=nbytes, form=int(form))
+    rc = native.kernels().die_kern_grn(json.dumps(geom).encode(), _ptr(xin), _ptr(gp), _ptr(bp), _ptr(out), _ptr(ws),
+                                       _ptr(lv), _stream())
+    _check(rc, "grn")
+    return out
+
+
 def softmax_rows(x, split=False):
     """x [rows, C] float -> (softmax stored bf16/split -> fp32 values, softmax fp32)."""
     import torch
