@@ -148,7 +148,8 @@ class Engine {
     (void)ran;
   }
   // Make host memory DMA-able for this engine (HIP: hipHostRegister); no-op elsewhere.  Returns
-  // the bytes actually pinned (0 when the engine needs no pinning).
+  // the bytes actually pinned (0 when the engine needs no pinning, or when the platform refuses to
+  // pin existing memory: the HIP engine then copies inputs from it through pinned buffers it owns).
   virtual size_t register_host_memory(void* p, size_t bytes) {
     (void)p;
     (void)bytes;

@@ -91,6 +91,8 @@ class HipEngine : public Engine {
     long long* h_lens_dev = nullptr;  // its device-side address
     DeviceMem<int> d_status;          // [status x max_batch][ntok x max_batch]
     PinnedMem<int> h_status;          // pinned
+    PinnedMem<uint8_t> h_bounce;      // this batch's inputs that came from unpinned shared memory
+    size_t bounce_bytes = 0;
     std::vector<DeviceMem<void>> d_prep;  // per-slot outputs of the PREP part's input-prep ops
     Event ev_gather;
     Event ev_h2d[kStageStreams];
@@ -159,6 +161,7 @@ class HipEngine : public Engine {
   void stager_loop();
   void completion_loop();
   void fill_gathered(BatchResult& r, Slot& sl, const Job& job);
+  bool in_unpinned(const void* p) const;
   hipStream_t result_stream(Slot& sl, hipStream_t cs);
   void dp_collectives(Slot& sl, int B, hipStream_t cs);
 
@@ -215,6 +218,10 @@ class HipEngine : public Engine {
   double weight_bcast_ms_ = 0;                 // RCCL weight broadcast at start-up (stats)
   std::atomic<long long> dp_collective_ops_{0};  // grouped per-batch gathers issued
   std::vector<void*> registered_;
+  // Host ranges the platform would not pin (register_host_memory): submit() copies a batch's
+  // inputs from them through the slot's own pinned bounce buffer.
+  std::vector<std::pair<const uint8_t*, size_t>> unpinned_;
+  std::atomic<long long> bounce_bytes_total_{0};
   float* ws_ = nullptr;  // executor 0's (autotune)
   size_t ws_bytes_ = 0;
   std::vector<std::vector<Tune>> tune_;  // [bucket][op]

@@ -278,11 +278,27 @@ HipEngine::~HipEngine() {
   pool_.reset();
 }
 
+// Called before the first submit().  Where the platform cannot pin memory the process already has
+// (a virtualised GPU: hipHostRegister fails), the range is remembered instead and submit() copies
+// what it takes from it through pinned memory of the engine's own (Slot::h_bounce, hipHostMalloc).
 size_t HipEngine::register_host_memory(void* p, size_t bytes) {
   HIP_CHECK(hipSetDevice(dev_));
-  HIP_CHECK(hipHostRegister(p, bytes, hipHostRegisterDefault));
-  registered_.push_back(p);
-  return bytes;
+  const hipError_t e = hipHostRegister(p, bytes, hipHostRegisterDefault);
+  if (e == hipSuccess) {
+    registered_.push_back(p);
+    return bytes;
+  }
+  (void)hipGetLastError();  // or the next kernel launch on this thread reports the refusal as its own
+  DIE_LOG(WARN, "hipHostRegister of " << bytes / 1048576.0 << " MiB refused (" << hipGetErrorString(e)
+                                      << "): inputs from it are staged through a pinned bounce buffer");
+  unpinned_.emplace_back(static_cast<const uint8_t*>(p), bytes);
+  return 0;
+}
+
+bool HipEngine::in_unpinned(const void* p) const {
+  for (const auto& r : unpinned_)
+    if (p >= r.first && p < r.first + r.second) return true;
+  return false;
 }
 
 // Token-id plans: an all-zero start-up input is all padding under the usual pad id 0, and the

@@ -106,6 +106,34 @@ void HipEngine::submit(std::vector<BatchItem> items, BatchDone done) {
     int wait_ticket[kStageStreams];  // per copy stream, the staged copy issued last covers the earlier ones
     bool copied[kStageStreams] = {};  // submit-time copies issued on that stream
     for (auto& w : wait_ticket) w = -1;
+    // Inputs in host memory the platform would not pin (register_host_memory) are copied into the
+    // slot's pinned bounce buffer first, 64-byte aligned one after another; it grows to the largest
+    // batch seen (the slot's earlier batch has completed, so nothing still reads it).
+    size_t bounce_off = 0;
+    if (!unpinned_.empty()) {
+      size_t need = 0;
+      for (const BatchItem& it : items) {
+        const void* p = it.text ? static_cast<const void*>(it.text) : static_cast<const void*>(it.input);
+        if (!p || !in_unpinned(p)) continue;
+        const size_t tb = std::min(it.text_len, text_cap_);
+        const size_t bytes = it.text ? (it.packed ? (tb + 1) / 2 : tb) : std::min(it.len, in_numel_) * sizeof(float);
+        need += (bytes + 63) / 64 * 64;
+      }
+      if (need > sl.bounce_bytes) {
+        sl.bounce_bytes = 0;
+        HIP_CHECK(sl.h_bounce.alloc(need));
+        sl.bounce_bytes = need;
+      }
+    }
+    auto pinned_src = [&](const void* p, size_t bytes) -> const void* {
+      if (unpinned_.empty() || !in_unpinned(p)) return p;
+      if (bounce_off + bytes > sl.bounce_bytes) throw std::runtime_error("input bounce buffer overrun");
+      uint8_t* d = sl.h_bounce + bounce_off;
+      std::memcpy(d, p, bytes);
+      bounce_off += (bytes + 63) / 64 * 64;
+      bounce_bytes_total_.fetch_add(static_cast<long long>(bytes), std::memory_order_relaxed);
+      return d;
+    };
     int rr = 0;
     for (int i = 0; i < B; ++i) {
       h_offs[i] = 0;
@@ -130,7 +158,8 @@ void HipEngine::submit(std::vector<BatchItem> items, BatchDone done) {
           h_offs[i] = static_cast<long long>(idx * text_cap_);
           h_poffs[i] = static_cast<long long>(idx * (text_cap_ / 2));
           const int si = rr++ % n_copy_streams_;
-          HIP_CHECK(hipMemcpyAsync(d_packed_ + idx * (text_cap_ / 2), items[i].text, (items[i].text_len + 1) / 2,
+          const size_t nb = (items[i].text_len + 1) / 2;
+          HIP_CHECK(hipMemcpyAsync(d_packed_ + idx * (text_cap_ / 2), pinned_src(items[i].text, nb), nb,
                                    hipMemcpyHostToDevice, s_stage_[si]));
           h2d_bytes_.fetch_add(static_cast<long long>((items[i].text_len + 1) / 2), std::memory_order_relaxed);
           copied[si] = true;
@@ -138,8 +167,8 @@ void HipEngine::submit(std::vector<BatchItem> items, BatchDone done) {
           const size_t idx = static_cast<size_t>(n_stage_) + static_cast<size_t>(slot) * max_batch_ + i;
           h_offs[i] = static_cast<long long>(idx * text_cap_);
           const int si = rr++ % n_copy_streams_;
-          HIP_CHECK(hipMemcpyAsync(d_text_ + idx * text_cap_, items[i].text, items[i].text_len, hipMemcpyHostToDevice,
-                                   s_stage_[si]));
+          HIP_CHECK(hipMemcpyAsync(d_text_ + idx * text_cap_, pinned_src(items[i].text, items[i].text_len),
+                                   items[i].text_len, hipMemcpyHostToDevice, s_stage_[si]));
           h2d_bytes_.fetch_add(static_cast<long long>(items[i].text_len), std::memory_order_relaxed);
           copied[si] = true;
         }
@@ -151,7 +180,9 @@ void HipEngine::submit(std::vector<BatchItem> items, BatchDone done) {
       const size_t n = std::min(items[i].len, in_numel_);
       float* dst = sl.d_in + static_cast<size_t>(i) * in_numel_;
       const int si = rr++ % n_copy_streams_;
-      if (n) HIP_CHECK(hipMemcpyAsync(dst, items[i].input, n * sizeof(float), hipMemcpyHostToDevice, s_stage_[si]));
+      if (n)
+        HIP_CHECK(hipMemcpyAsync(dst, pinned_src(items[i].input, n * sizeof(float)), n * sizeof(float),
+                                 hipMemcpyHostToDevice, s_stage_[si]));
       h2d_bytes_.fetch_add(static_cast<long long>(n * sizeof(float)), std::memory_order_relaxed);
       if (n < in_numel_) HIP_CHECK(hipMemsetAsync(dst + n, 0, (in_numel_ - n) * sizeof(float), s_stage_[si]));
       copied[si] = true;

@@ -15,6 +15,7 @@ Json HipEngine::stats() const {
   j["device_id"] = dev_;
   j["h2d_bytes"] = h2d_bytes_.load();
   j["d2h_bytes"] = d2h_bytes_.load();
+  j["h2d_bounce_bytes"] = bounce_bytes_total_.load();  // of h2d_bytes: copied through pinned bounce buffers first
   j["graph_replays"] = graph_replays_.load();
   j["device_busy_ms"] = device_ms_total_.load();
   // per batch: compute stream waiting for the batch's PREP (copies + decode) / idle before it was submitted

@@ -7,7 +7,8 @@
 //   * an input arena: the leader's request staging buffers (SamplePool) are carved from it, so a
 //     follower reads its shard's inputs from the very pages the HTTP thread wrote (each process
 //     hipHostRegister()s the arena, and every GPU pulls its shard over its own PCIe link -- no
-//     routing through GPU 0);
+//     routing through GPU 0; where the platform cannot pin a mapped segment, each rank's engine
+//     copies its shard through pinned buffers of its own instead);
 //   * gather slots for the host communicator (CPU engines / tests);
 //   * per-rank sub-batch rings: EVERY rank's worker ingests HTTP (the ranks share one listening port
 //     through SO_REUSEPORT), parses into the arena and queues its requests as a sub-batch; the

@@ -46,6 +46,15 @@ def test_dp_engine_rccl_world1_matches_plain_engine(native, models, dp_path):
     for B in (1, 3, 8):
         x = r.synthetic_input(B, cfg, seed=B).reshape(B, -1)
         np.testing.assert_array_equal(dp.run(x), plain.run(x))
+    if dp_path != "solo":
+        # every input came from the shared arena: either the rank pinned it in place, or (where the
+        # platform cannot pin mapped memory) each byte went through the engine's pinned bounce buffers
+        info = dp.refresh_info()
+        assert info["h2d_bytes"] == (1 + 3 + 8) * x.shape[1] * 4
+        if info["dp_pinned_bytes"]:
+            assert info["dp_pinned_bytes"] == info["dp_pin_request_bytes"] and info["h2d_bounce_bytes"] == 0
+        else:
+            assert info["h2d_bounce_bytes"] == info["h2d_bytes"]
     dp.close()
     plain.close()
 
