@@ -199,6 +199,8 @@ int die_kern_conv(const char* geom, uint64_t x, uint64_t w, uint64_t bias, uint6
     if (auto* v = j.find("row_parts")) a.row_parts = P<const float>(static_cast<uint64_t>(v->as_int()));
     if (auto* v = j.find("stats_out")) a.stats_out = P<float>(static_cast<uint64_t>(v->as_int()));
     if (auto* v = j.find("ln_eps")) a.ln_eps = static_cast<float>(v->as_double());
+    if (auto* v = j.find("clip_lo")) a.clip_lo = static_cast<float>(v->as_double());  // relu == 3 (Clip)
+    if (auto* v = j.find("clip_hi")) a.clip_hi = static_cast<float>(v->as_double());
     if (tile < 0) tile = kern::choose_tile(a.M, a.N, a.K);
     return static_cast<int>(kern::conv_igemm(a, tile, S(stream)));
   } catch (...) {

@@ -74,7 +74,8 @@ hipError_t conv_igemm(const ConvArgs& a, int cfg, hipStream_t s) {
   if (a.out2 && (!a.scale2 || !a.shift2)) return hipErrorInvalidValue;
   if ((a.row_stats || a.row_parts) && !a.col_sum) return hipErrorInvalidValue;
   // epilogue statistics: whole 64-column groups in one 8-lane DPP group; readers: the fp32 (split)
-  // kernels' LDS-staged epilogue (the launcher also rules out the two-kernel split-K form)
+  // kernels' LDS-staged epilogue.  Both also run in the two-kernel split-K form: splitk_epilogue_kernel
+  // maps 8 consecutive threads to a group, and merges a reader's row itself (row_parts_direct)
   if (a.stats_out && a.N % 64 != 0) return hipErrorInvalidValue;
   if (a.row_parts && (a.row_stats || !a.split || a.N % 8 != 0 || a.K % 64 != 0)) return hipErrorInvalidValue;
   if (a.splits > 1 && (a.N % 8 != 0 || !a.ws)) return hipErrorInvalidValue;

@@ -1021,8 +1021,11 @@ __global__ __launch_bounds__(256) void conv_glds_kernel(const ConvArgs p, const 
     StreamK sk;
     sk.nk = nk_total;
     sk.I = static_cast<long long>(ntm) * ntn * nk_total;
-    sk.P = static_cast<int>(gridDim.x);
+    // no more blocks than iterations (a tiny problem, a small live batch): a block with an empty range
+    // was counted as a contributor of the tile it starts in, which then was never reduced
+    sk.P = sk.I < static_cast<long long>(gridDim.x) ? static_cast<int>(sk.I) : static_cast<int>(gridDim.x);
     const int nb = sk.P, b = blockIdx.x;
+    if (b >= nb) return;  // whole block, before any barrier
     const int q = nb >> 3, r = nb & 7, x = b & 7;
     const int id = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
     long long it = sk.start(id);
