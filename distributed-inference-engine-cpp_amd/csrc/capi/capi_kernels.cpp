@@ -78,6 +78,7 @@ std::string plan_dump(const Plan& p) {
     l.i("out", o.out).i("out2", o.out2).i("out3", o.out3).i("out_f32", o.out_f32).i("out_stats", o.out_stats);
     l.off("w_off", o.w_off).off("bias_off", o.bias_off).off("s2_off", o.s2_off).off("b2_off", o.b2_off);
     l.off("scale_off", o.scale_off).off("shift_off", o.shift_off).off("tap_w_off", o.tap_w_off);
+    l.off("mfma_w_off", o.mfma_w_off).i("mfma", o.mfma).i("mfma_wplane", o.mfma_wplane);
     l.off("type_off", o.type_off).off("w2_off", o.w2_off).off("bias2_off", o.bias2_off).off("colsum_off", o.colsum_off);
     const kern::ConvArgs& a = o.conv;
     l.i("conv.B", a.B).i("conv.H", a.H).i("conv.W", a.W).i("conv.Cin", a.Cin).i("conv.Ho", a.Ho).i("conv.Wo", a.Wo);
@@ -503,6 +504,27 @@ int die_kern_dwconv(const char* geom, int tiled, uint64_t x, uint64_t w, uint64_
   }
 }
 
+// Grouped 3x3 conv on the MFMA kernel (kern::grouped_conv_mfma) with the whole GConvArgs epilogue:
+// w_packed = the bf16 weights of kern::gconv_mfma_pack, wplane = elements from the hi to the lo plane
+// (split mode).  Returns the hipError_t (1 = hipErrorInvalidValue: outside the scope, nothing launched).
+int die_kern_gconv_mfma(const char* geom, uint64_t x, uint64_t w_packed, long long wplane, uint64_t bias, uint64_t res,
+                        uint64_t out, uint64_t out_f32, uint64_t live, uint64_t stream) {
+  try {
+    kern::GConvArgs a = gconv_geometry(geom);
+    a.x = P<const uint16_t>(x);
+    a.wp = P<const uint16_t>(w_packed);
+    a.wplane = wplane;
+    a.bias = P<const float>(bias);
+    a.res = P<const uint16_t>(res);
+    a.out = P<uint16_t>(out);
+    a.out_f32 = P<float>(out_f32);
+    a.live = P<const long long>(live);
+    return static_cast<int>(kern::grouped_conv_mfma(a, S(stream)));
+  } catch (...) {
+    return -1;
+  }
+}
+
 // GroupNorm / InstanceNorm (kern::group_norm): geom's keys are the scalar members of GroupNormArgs.
 // Returns the hipError_t (1 = hipErrorInvalidValue: bad arguments, nothing launched).
 long long die_groupnorm_workspace_bytes(int B, int HW, int C, int G) {
@@ -754,6 +776,7 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
       }
       if (o.kind == PlanOp::GCONV) {
         e["tiled"] = o.tiled != 0;  // in the scope of the tiled depthwise kernel (kernels/dwconv.hip)
+        e["mfma"] = o.mfma != 0;    // in the scope of the MFMA grouped 3x3 kernel (kernels/gconv_mfma.hip)
         e["KH"] = o.kh;
         e["stride"] = o.sh;
         e["groups"] = o.groups;

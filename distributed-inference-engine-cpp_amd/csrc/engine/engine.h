@@ -254,6 +254,10 @@ struct EngineOptions {
   // false: on gconv_kernel like every other grouped conv -- the same bits, for comparisons in one
   // process (profiles/convnext.md)
   bool tiled_dwconv = true;
+  // grouped 3x3 convs of width 4 / 8 / 16 / 32 (PlanOp::mfma) on the MFMA kernel (kernels/gconv_mfma.hip);
+  // false: on gconv_kernel with its fp32 weights -- the same bars, not the same bits
+  // (profiles/gconv_mfma.md)
+  bool mfma_gconv = true;
   bool tune_cold = true;          // autotune with an L2 scrub before each timing (false: back-to-back)
   // after the isolated-launch autotune, time each conv's front runners in place inside eager
   // forwards (input warm from its producer, weights where the previous forward left them) and keep

@@ -117,6 +117,13 @@ struct PlanOp {
   // picks the kernel (EngineOptions::tiled_dwconv), w_off stays valid for kern::grouped_conv
   int tiled = 0;
   size_t tap_w_off = SIZE_MAX;
+  // GCONV in the scope of the MFMA grouped 3x3 kernel (kern::grouped_conv_mfma: 3x3, dilation 1, stride
+  // 1 or 2, Cin == Cout, group width 4 / 8 / 16 / 32): mfma = 1, mfma_w_off = the weights packed by
+  // kern::gconv_mfma_pack (bf16; fp32 mode: the lo plane mfma_wplane elements after the hi plane); the
+  // engine picks the kernel (EngineOptions::mfma_gconv), w_off stays valid for kern::grouped_conv
+  int mfma = 0;
+  size_t mfma_w_off = SIZE_MAX;
+  long long mfma_wplane = 0;
   float clip_lo = 0.f, clip_hi = 0.f;  // act == 3 (Clip) of AFFINE / GCONV
   long long rows_per_sample = 0;  // AFFINE / LAYERNORM: rows of C per sample
   // transformer ops: sequence length, heads, head dim, column offsets / pitches of in/in2/in3

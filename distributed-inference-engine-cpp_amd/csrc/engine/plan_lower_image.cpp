@@ -15,7 +15,8 @@
 //    with no other reader of the GEMM (layer scale) is folded into its weights and bias.  The
 //    decomposed LayerNorm over axis 1 of an NCHW image is the LAYERNORM op over the image's rows
 //    (lower_reduce_mean).  Depthwise 5x5 / 7x7 stride-1 convs are marked for the tiled kernel
-//    (PlanOp::tiled).  Rejected with a report line: other 4-D permutes of an image, the view as the
+//    (PlanOp::tiled), grouped 3x3 convs of width 4 / 8 / 16 / 32 for the MFMA kernel (PlanOp::mfma).
+//    Rejected with a report line: other 4-D permutes of an image, the view as the
 //    graph output, a LayerNorm over any other axis.
 // Standalone BatchNormalization / Relu / Add that fold into nothing become affine / add / relu kernels.
 #include "planner.h"
@@ -398,6 +399,23 @@ void Planner::lower_gconv(int idx) {
       for (int tap = 0; tap < KH * KW; ++tap) wt_tap[static_cast<size_t>(tap) * Cout + co] = w[static_cast<size_t>(co) * KH * KW + tap];
     p.tiled = 1;
     p.tap_w_off = push_f32(wt_tap);
+  }
+  {  // grouped 3x3 in the scope of the MFMA kernel: every (width, stride) class of it is marked
+     // (profiles/gconv_mfma.md)
+    kern::GConvArgs ga;
+    ga.Cin = x.C;
+    ga.Cout = Cout;
+    ga.groups = G;
+    ga.KH = KH;
+    ga.KW = KW;
+    ga.stride = s;
+    ga.dil = d;
+    ga.pad_h = static_cast<int>(pads[0]);
+    ga.pad_w = static_cast<int>(pads[1]);
+    if (kern::grouped_conv_mfma_supported(ga)) {
+      p.mfma = 1;
+      p.mfma_w_off = push_bf16(kern::gconv_mfma_pack(wt.f.data(), scale.data(), Cout, cpg, opt_.split, p.mfma_wplane));
+    }
   }
   p.groups = G;
   p.C = x.C;

@@ -6,6 +6,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstring>
+#include <vector>
+
 namespace die {
 namespace kern {
 
@@ -175,8 +178,58 @@ struct GConvArgs {
   float clip_lo = 0.f, clip_hi = 0.f;
   int split = 0;
   const long long* live = nullptr;
+  // grouped_conv_mfma only: the packed bf16 weights (gconv_mfma_pack) and, in split mode, the distance
+  // in elements from the hi plane to the lo plane
+  const uint16_t* wp = nullptr;
+  long long wplane = 0;
 };
 hipError_t grouped_conv(const GConvArgs& a, hipStream_t s);
+// Grouped 3x3 convolution on the matrix cores (gconv_mfma.hip): the same arguments and epilogue, the
+// weights in wp / wplane instead of w.  Scope: 3x3, dilation 1, stride 1 or 2, pads >= 0, Cin == Cout
+// == C, C / groups in {4, 8, 16, 32}, C % 16 == 0; anything else returns hipErrorInvalidValue and
+// launches nothing.
+inline bool grouped_conv_mfma_supported(const GConvArgs& a) {  // host only: the planner's mark rule too
+  if (a.KH != 3 || a.KW != 3 || a.dil != 1 || (a.stride != 1 && a.stride != 2) || a.pad_h < 0 || a.pad_w < 0) return false;
+  if (a.groups < 1 || a.Cin != a.Cout || a.Cout < 16 || a.Cout % 16 || a.Cout % a.groups) return false;
+  const int w = a.Cout / a.groups;
+  return w == 4 || w == 8 || w == 16 || w == 32;
+}
+hipError_t grouped_conv_mfma(const GConvArgs& a, hipStream_t s);
+// Weights of grouped_conv_mfma: fp32 [C][w][3][3] (ONNX order, w = C / groups; scale: optional [C]
+// factor per output channel, folded in before the bf16 / split rounding) -> [C / 16][16][Kb] bf16 with
+// k = tap * kc + ci; kc = 16, Kb = 160 for w <= 16 (ci counts the bundle's 16 input channels, zeros off
+// the block diagonal and in tap 9), kc = 32, Kb = 288 for w = 32.  split: the hi plane, then the lo
+// plane `wplane` elements after it (0 when not split).  ops/kernels.py pack_gconv_mfma_weight mirrors it.
+inline std::vector<uint16_t> gconv_mfma_pack(const float* wt, const float* scale, int C, int w, bool split,
+                                             long long& wplane) {
+  const int kc = w == 32 ? 32 : 16, Kb = kc == 16 ? 160 : 288;
+  const size_t n = static_cast<size_t>(C) * Kb;
+  std::vector<uint16_t> q(n * (split ? 2 : 1), 0);
+  auto bf = [](float f) {  // round to nearest even, like the device's f2bf
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return static_cast<uint16_t>((u >> 16) | 0x40);
+    return static_cast<uint16_t>((u + 0x7fffu + ((u >> 16) & 1)) >> 16);
+  };
+  for (int co = 0; co < C; ++co) {
+    const int ci0 = kc == 32 ? 0 : (co / w) * w - (co / 16) * 16;  // the group's first channel within the bundle's inputs
+    for (int ci = 0; ci < w; ++ci)
+      for (int tap = 0; tap < 9; ++tap) {
+        const float v = wt[(static_cast<size_t>(co) * w + ci) * 9 + tap] * (scale ? scale[co] : 1.f);
+        const size_t k = static_cast<size_t>(co) * Kb + tap * kc + ci0 + ci;
+        const uint16_t hi = bf(v);
+        q[k] = hi;
+        if (split) {
+          const uint32_t hu = static_cast<uint32_t>(hi) << 16;
+          float hf;
+          std::memcpy(&hf, &hu, 4);
+          q[n + k] = bf(v - hf);
+        }
+      }
+  }
+  wplane = split ? static_cast<long long>(n) : 0;
+  return q;
+}
 // Tiled depthwise convolution (dwconv.hip): the same arguments and epilogue, but w = fp32 [KH*KW][C]
 // (tap-major).  Scope: groups == Cin == Cout, C % 8 == 0, stride 1, dilation 1, 5x5 / 7x7, pads >= 0;
 // anything else returns hipErrorInvalidValue and launches nothing.  Same bits as grouped_conv.

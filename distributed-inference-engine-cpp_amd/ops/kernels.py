@@ -865,6 +865,65 @@ def depthwise_conv(x_nhwc, w, bias=None, pads=(0, 0, 0, 0), stride=1, dilation=1
     return out, of
 
 
+def pack_gconv_mfma_weight(w, split=False):
+    """[C, cw, 3, 3] float (cw = C / groups in {4, 8, 16, 32}) -> the weights of the MFMA grouped conv kernel,
+    the torch mirror of kern::gconv_mfma_pack (csrc/kernels/kernels.h): [C/16][16][Kb] bf16 with k = tap * kc + ci;
+    kc = 16, Kb = 160 for cw <= 16 (ci counts the bundle's 16 input channels: zeros off the block diagonal and in
+    tap 9), kc = 32, Kb = 288 for cw = 32.  split: [2][C][Kb], the hi plane, then the lo plane.
+    Returns (packed, plane distance in elements: 0 when not split)."""
+    import torch
+
+    C, cw = int(w.shape[0]), int(w.shape[1])
+    kc = 32 if cw == 32 else 16
+    Kb = 160 if kc == 16 else 288
+    co = torch.arange(C, device=w.device)
+    ci0 = torch.zeros_like(co) if kc == 32 else (co // cw) * cw - (co // 16) * 16
+    k = (torch.arange(9, device=w.device)[None, None, :] * kc + ci0[:, None, None]
+         + torch.arange(cw, device=w.device)[None, :, None])  # [C][cw][tap]
+    full = torch.zeros((C, Kb), dtype=torch.float32, device=w.device)
+    full.scatter_(1, k.reshape(C, -1), w.float().reshape(C, -1))
+    return (split_planes(full), C * Kb) if split else (full.to(torch.bfloat16), 0)
+
+
+def grouped_conv_mfma(x_nhwc, w, bias=None, pads=(0, 0, 0, 0), stride=1, dilation=1, clip=None, relu=False,
+                      residual=None, split=False, want_f32=False, live=None, fill=None, groups=1):
+    """Grouped conv with the whole epilogue on the MFMA kernel (csrc/kernels/gconv_mfma.hip).  x [B,H,W,C] (bf16,
+    or any float dtype with split), w [Cout, Cin/groups, k, k] float, pads [top, left, bottom, right], residual
+    [B,Ho,Wo,Cout] added after the activation, live: number of leading samples to compute (a device-side count; the
+    others keep `fill`).  Returns (stored planes: bf16 [B,Ho,Wo,Cout], or [2,B,Ho,Wo,Cout] hi / lo when split; f32
+    output or None).  A geometry outside the kernel's scope raises NativeError with hipError 1 and launches nothing."""
+    import torch
+
+    B, H, W, C = x_nhwc.shape
+    Cout, cpg, KH, KW = w.shape
+    Ho = (H + pads[0] + pads[2] - dilation * (KH - 1) - 1) // stride + 1
+    Wo = (W + pads[1] + pads[3] - dilation * (KW - 1) - 1) // stride + 1
+    dev = x_nhwc.device
+    xin = _in(x_nhwc, split) if split else x_nhwc.to(torch.bfloat16).contiguous()
+    in_scope = (KH == 3 and KW == 3 and cpg in (4, 8, 16, 32) and Cout == C and cpg * groups == C)
+    # outside the scope nothing is read: the launcher refuses the geometry before it looks at the weights
+    wp, wplane = pack_gconv_mfma_weight(w, split) if in_scope else (w.float().contiguous(), 1)
+    bp = None if bias is None else bias.float().contiguous()
+    rp = None
+    if residual is not None:
+        rp = _in(residual, split) if split else residual.to(torch.bfloat16).contiguous()
+    out = torch.empty(((2,) if split else ()) + (B, Ho, Wo, Cout), dtype=torch.bfloat16, device=dev)
+    of = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32, device=dev) if want_f32 else None
+    if fill is not None:
+        out.fill_(fill)
+        if of is not None:
+            of.fill_(fill)
+    lv = None if live is None else torch.tensor([int(live)], dtype=torch.int64, device=dev)
+    act = 3 if clip is not None else (1 if relu else 0)
+    lo, hi = clip if clip is not None else (0.0, 0.0)
+    geom = dict(B=B, H=H, W=W, Cin=C, Ho=Ho, Wo=Wo, Cout=Cout, groups=groups, KH=KH, KW=KW, stride=stride,
+                dil=dilation, pad_h=pads[0], pad_w=pads[1], act=act, clip_lo=float(lo), clip_hi=float(hi), split=int(split))
+    rc = native.kernels().die_kern_gconv_mfma(json.dumps(geom).encode(), _ptr(xin), _ptr(wp), int(wplane), _ptr(bp),
+                                              _ptr(rp), _ptr(out), _ptr(of), _ptr(lv), _stream())
+    _check(rc, "grouped_conv_mfma")
+    return out, of
+
+
 GN_ACTS = {None: 0, "none": 0, "relu": 1, "silu": 2}
 
 
