@@ -100,6 +100,7 @@ EngineOptions engine_opts(const Json& j) {
   e.fuse_gap_fc = jget<bool>(j, "fuse_gap_fc", e.fuse_gap_fc);
   e.fold_layernorm = jget<bool>(j, "fold_layernorm", e.fold_layernorm);
   e.tiled_dwconv = jget<bool>(j, "tiled_dwconv", e.tiled_dwconv);
+  e.poly_dwconv = jget<bool>(j, "poly_dwconv", e.poly_dwconv);
   e.mfma_gconv = jget<bool>(j, "mfma_gconv", e.mfma_gconv);
   e.ln_stats_epilogue = jget<bool>(j, "ln_stats_epilogue", e.ln_stats_epilogue);
   e.tune_in_graph = jget<bool>(j, "tune_in_graph", e.tune_in_graph);

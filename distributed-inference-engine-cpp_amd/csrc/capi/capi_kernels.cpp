@@ -90,7 +90,7 @@ std::string plan_dump(const Plan& p) {
     l.i("conv.probe", a.probe).i("conv.tail", a.tail).i("conv.sk", a.sk);
     l.i("tile_bmax", o.tile_bmax).i("C", o.C).i("H", o.H).i("W", o.W).i("Ho", o.Ho).i("Wo", o.Wo).i("Cp", o.Cp);
     l.i("kh", o.kh).i("kw", o.kw).i("sh", o.sh).i("sw", o.sw).i("ph", o.ph).i("pw", o.pw).i("is_max", o.is_max);
-    l.i("cip", o.cip).i("act", o.act).i("ld_store", o.ld_store).i("groups", o.groups).i("tiled", o.tiled);
+    l.i("cip", o.cip).i("act", o.act).i("ld_store", o.ld_store).i("groups", o.groups).i("tiled", o.tiled).i("poly", o.poly);
     l.f("clip_lo", o.clip_lo).f("clip_hi", o.clip_hi).i("rows_per_sample", o.rows_per_sample);
     l.i("S", o.S).i("nh", o.nh).i("hd", o.hd).i("gidx", o.gidx);
     for (int r = 0; r < 3; ++r) l.i(("col" + std::to_string(r)).c_str(), o.col[r]).i(("ld" + std::to_string(r)).c_str(), o.ld[r]);
@@ -504,6 +504,26 @@ int die_kern_dwconv(const char* geom, int tiled, uint64_t x, uint64_t w, uint64_
   }
 }
 
+// Depthwise conv on the polyphase tiled kernel (kern::dwconv_poly) with the whole GConvArgs epilogue:
+// w = fp32 [KH*KW][C], as for the tiled kernel.  Returns the hipError_t (1 = hipErrorInvalidValue: outside
+// the scope, nothing launched).
+int die_kern_dwconv_poly(const char* geom, uint64_t x, uint64_t w, uint64_t bias, uint64_t res, uint64_t out,
+                         uint64_t out_f32, uint64_t live, uint64_t stream) {
+  try {
+    kern::GConvArgs a = gconv_geometry(geom);
+    a.x = P<const uint16_t>(x);
+    a.w = P<const float>(w);
+    a.bias = P<const float>(bias);
+    a.res = P<const uint16_t>(res);
+    a.out = P<uint16_t>(out);
+    a.out_f32 = P<float>(out_f32);
+    a.live = P<const long long>(live);
+    return static_cast<int>(kern::dwconv_poly(a, S(stream)));
+  } catch (...) {
+    return -1;
+  }
+}
+
 // Grouped 3x3 conv on the MFMA kernel (kern::grouped_conv_mfma) with the whole GConvArgs epilogue:
 // w_packed = the bf16 weights of kern::gconv_mfma_pack, wplane = elements from the hi to the lo plane
 // (split mode).  Returns the hipError_t (1 = hipErrorInvalidValue: outside the scope, nothing launched).
@@ -776,6 +796,7 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
       }
       if (o.kind == PlanOp::GCONV) {
         e["tiled"] = o.tiled != 0;  // in the scope of the tiled depthwise kernel (kernels/dwconv.hip)
+        e["poly"] = o.poly != 0;    // marked for the polyphase depthwise kernel (kernels/dwconv_poly.hip)
         e["mfma"] = o.mfma != 0;    // in the scope of the MFMA grouped 3x3 kernel (kernels/gconv_mfma.hip)
         e["KH"] = o.kh;
         e["stride"] = o.sh;

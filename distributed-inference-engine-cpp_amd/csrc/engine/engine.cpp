@@ -310,6 +310,7 @@ Json engine_options_json(const EngineOptions& o) {
   j["fuse_gap_fc"] = o.fuse_gap_fc;
   j["fold_layernorm"] = o.fold_layernorm;
   j["tiled_dwconv"] = o.tiled_dwconv;
+  j["poly_dwconv"] = o.poly_dwconv;
   j["mfma_gconv"] = o.mfma_gconv;
   j["ln_stats_epilogue"] = o.ln_stats_epilogue;
   j["tune_in_graph"] = o.tune_in_graph;

@@ -254,6 +254,9 @@ struct EngineOptions {
   // false: on gconv_kernel like every other grouped conv -- the same bits, for comparisons in one
   // process (profiles/convnext.md)
   bool tiled_dwconv = true;
+  // depthwise 3x3 (stride 1 / 2) and stride-2 5x5 convs (PlanOp::poly) on the polyphase tiled kernel
+  // (kernels/dwconv_poly.hip); false: on gconv_kernel -- the same bits (profiles/dwconv_poly.md)
+  bool poly_dwconv = true;
   // grouped 3x3 convs of width 4 / 8 / 16 / 32 (PlanOp::mfma) on the MFMA kernel (kernels/gconv_mfma.hip);
   // false: on gconv_kernel with its fp32 weights -- the same bars, not the same bits
   // (profiles/gconv_mfma.md)

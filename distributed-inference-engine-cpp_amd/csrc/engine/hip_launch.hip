@@ -400,6 +400,9 @@ hipError_t HipEngine::launch_op(const PlanOp& op, size_t op_index, int B, int s,
       if (op.tiled && opt_.tiled_dwconv) {
         g.w = prm(op.tap_w_off);
         e = kern::dwconv_tiled(g, st);
+      } else if (op.poly && opt_.poly_dwconv) {
+        g.w = prm(op.tap_w_off);
+        e = kern::dwconv_poly(g, st);
       } else if (op.mfma && opt_.mfma_gconv) {
         g.wp = reinterpret_cast<const uint16_t*>(prm(op.mfma_w_off));
         g.wplane = op.mfma_wplane;

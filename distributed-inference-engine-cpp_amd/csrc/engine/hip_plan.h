@@ -117,6 +117,11 @@ struct PlanOp {
   // picks the kernel (EngineOptions::tiled_dwconv), w_off stays valid for kern::grouped_conv
   int tiled = 0;
   size_t tap_w_off = SIZE_MAX;
+  // GCONV in the scope of the polyphase depthwise kernel (kern::dwconv_poly: depthwise, dilation 1,
+  // 3x3 at stride 1 / 2 or 5x5 at stride 2) whose (window, stride) class is turned on
+  // (kern::dwconv_poly_class_on): poly = 1 and tap_w_off as above; never together with tiled.  The
+  // engine picks the kernel (EngineOptions::poly_dwconv), w_off stays valid for kern::grouped_conv
+  int poly = 0;
   // GCONV in the scope of the MFMA grouped 3x3 kernel (kern::grouped_conv_mfma: 3x3, dilation 1, stride
   // 1 or 2, Cin == Cout, group width 4 / 8 / 16 / 32): mfma = 1, mfma_w_off = the weights packed by
   // kern::gconv_mfma_pack (bf16; fp32 mode: the lo plane mfma_wplane elements after the hi plane); the

@@ -15,7 +15,8 @@
 //    with no other reader of the GEMM (layer scale) is folded into its weights and bias.  The
 //    decomposed LayerNorm over axis 1 of an NCHW image is the LAYERNORM op over the image's rows
 //    (lower_reduce_mean).  Depthwise 5x5 / 7x7 stride-1 convs are marked for the tiled kernel
-//    (PlanOp::tiled), grouped 3x3 convs of width 4 / 8 / 16 / 32 for the MFMA kernel (PlanOp::mfma).
+//    (PlanOp::tiled), grouped 3x3 convs of width 4 / 8 / 16 / 32 for the MFMA kernel (PlanOp::mfma),
+//    depthwise 3x3 and stride-2 5x5 convs for the polyphase kernel (PlanOp::poly).
 //    Rejected with a report line: other 4-D permutes of an image, the view as the
 //    graph output, a LayerNorm over any other axis.
 // Standalone BatchNormalization / Relu / Add that fold into nothing become affine / add / relu kernels.
@@ -399,6 +400,26 @@ void Planner::lower_gconv(int idx) {
       for (int tap = 0; tap < KH * KW; ++tap) wt_tap[static_cast<size_t>(tap) * Cout + co] = w[static_cast<size_t>(co) * KH * KW + tap];
     p.tiled = 1;
     p.tap_w_off = push_f32(wt_tap);
+  }
+  {  // depthwise 3x3 / strided 5x5 in the scope of the polyphase kernel: the (window, stride) classes that
+     // measured faster than gconv_kernel are marked (profiles/dwconv_poly.md)
+    kern::GConvArgs ga;
+    ga.Cin = x.C;
+    ga.Cout = Cout;
+    ga.groups = G;
+    ga.KH = KH;
+    ga.KW = KW;
+    ga.stride = s;
+    ga.dil = d;
+    ga.pad_h = static_cast<int>(pads[0]);
+    ga.pad_w = static_cast<int>(pads[1]);
+    if (kern::dwconv_poly_supported(ga) && kern::dwconv_poly_class_on(KH, s)) {
+      std::vector<float> wt_tap(static_cast<size_t>(KH) * KW * Cout);
+      for (int co = 0; co < Cout; ++co)
+        for (int tap = 0; tap < KH * KW; ++tap) wt_tap[static_cast<size_t>(tap) * Cout + co] = w[static_cast<size_t>(co) * KH * KW + tap];
+      p.poly = 1;
+      p.tap_w_off = push_f32(wt_tap);
+    }
   }
   {  // grouped 3x3 in the scope of the MFMA kernel: every (width, stride) class of it is marked
      // (profiles/gconv_mfma.md)

@@ -235,6 +235,21 @@ inline std::vector<uint16_t> gconv_mfma_pack(const float* wt, const float* scale
 // anything else returns hipErrorInvalidValue and launches nothing.  Same bits as grouped_conv.
 bool dwconv_tiled_supported(const GConvArgs& a);
 hipError_t dwconv_tiled(const GConvArgs& a, hipStream_t s);
+// Polyphase tiled depthwise convolution (dwconv_poly.hip): the same arguments, epilogue and tap-major
+// weights as dwconv_tiled.  Scope: groups == Cin == Cout, C % 8 == 0, dilation 1, pads >= 0, (window,
+// stride) in {(3x3, 1), (3x3, 2), (5x5, 2)}; anything else returns hipErrorInvalidValue and launches
+// nothing.  Same bits as grouped_conv.
+inline bool dwconv_poly_supported(const GConvArgs& a) {  // host only
+  return a.groups == a.Cin && a.groups == a.Cout && a.Cout % 8 == 0 && a.Cout >= 8 && a.dil == 1 && a.KH == a.KW &&
+         a.pad_h >= 0 && a.pad_w >= 0 && ((a.KH == 3 && (a.stride == 1 || a.stride == 2)) || (a.KH == 5 && a.stride == 2));
+}
+// The planner's mark rule (PlanOp::poly): the (window, stride) classes of the scope in which the kernel
+// beat gconv_kernel by more than the spread on every model shape at batch 8 and 32
+// (profiles/dwconv_poly.md).  A class that is off stays reachable through dwconv_poly itself.
+inline bool dwconv_poly_class_on(int k, int stride) {
+  return (k == 3 && stride == 1) || (k == 3 && stride == 2) || (k == 5 && stride == 2);
+}
+hipError_t dwconv_poly(const GConvArgs& a, hipStream_t s);
 
 // GroupNorm / InstanceNorm of an NHWC image x [B][HW][C] (groupnorm.hip), per (sample, group):
 //   y = act((x - mean[b, g]) * rsqrt(var[b, g] + eps) * gamma[c] + beta[c])

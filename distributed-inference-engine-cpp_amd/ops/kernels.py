@@ -823,7 +823,7 @@ def grouped_conv(x_nhwc, w, bias=None, stride=1, pads=(0, 0, 0, 0), groups=1, cl
 
 
 def depthwise_conv(x_nhwc, w, bias=None, pads=(0, 0, 0, 0), stride=1, dilation=1, clip=None, relu=False, residual=None,
-                   split=False, want_f32=False, live=None, fill=None, tiled=True, groups=None):
+                   split=False, want_f32=False, live=None, fill=None, tiled=True, groups=None, _poly=False):
     """Depthwise conv with the whole epilogue, on the tiled kernel (csrc/kernels/dwconv.hip; tiled=False:
     the same call on gconv_kernel, for comparison).  x [B,H,W,C] (bf16, or any float dtype with split),
     w [C,1,k,k] float, pads [top, left, bottom, right], residual [B,Ho,Wo,C] added after the activation,
@@ -859,10 +859,23 @@ def depthwise_conv(x_nhwc, w, bias=None, pads=(0, 0, 0, 0), stride=1, dilation=1
     geom = dict(B=B, H=H, W=W, Cin=C, Ho=Ho, Wo=Wo, Cout=Cout, groups=C if groups is None else groups, KH=KH, KW=KW,
                 stride=stride, dil=dilation, pad_h=pads[0], pad_w=pads[1], act=act, clip_lo=float(lo), clip_hi=float(hi),
                 split=int(split))
-    rc = native.kernels().die_kern_dwconv(json.dumps(geom).encode(), int(tiled), _ptr(xin), _ptr(wp), _ptr(bp), _ptr(rp),
-                                          _ptr(out), _ptr(of), _ptr(lv), _stream())
-    _check(rc, "depthwise_conv")
+    if _poly:
+        rc = native.kernels().die_kern_dwconv_poly(json.dumps(geom).encode(), _ptr(xin), _ptr(wp), _ptr(bp), _ptr(rp),
+                                                   _ptr(out), _ptr(of), _ptr(lv), _stream())
+    else:
+        rc = native.kernels().die_kern_dwconv(json.dumps(geom).encode(), int(tiled), _ptr(xin), _ptr(wp), _ptr(bp),
+                                              _ptr(rp), _ptr(out), _ptr(of), _ptr(lv), _stream())
+    _check(rc, "depthwise_conv_poly" if _poly else "depthwise_conv")
     return out, of
+
+
+def depthwise_conv_poly(x_nhwc, w, bias=None, pads=(0, 0, 0, 0), stride=1, dilation=1, clip=None, relu=False,
+                        residual=None, split=False, want_f32=False, live=None, fill=None, tiled=True, groups=None):
+    """depthwise_conv on the polyphase tiled kernel (csrc/kernels/dwconv_poly.hip): 3x3 at stride 1 / 2 and 5x5 at
+    stride 2, the same arguments (tiled=False: the same call on gconv_kernel) and the same return.  A geometry
+    outside the kernel's scope raises NativeError with hipError 1 and launches nothing."""
+    return depthwise_conv(x_nhwc, w, bias, pads, stride, dilation, clip, relu, residual, split, want_f32, live, fill,
+                          tiled, groups, _poly=bool(tiled))
 
 
 def pack_gconv_mfma_weight(w, split=False):
