@@ -65,6 +65,7 @@ die::EngineOptions engine_options_from_flags(const die::Flags& f, const std::str
   eo.tiled_dwconv = !f.b("no-tiled-dwconv");
   eo.poly_dwconv = !f.b("no-poly-dwconv");
   eo.mfma_gconv = !f.b("no-mfma-gconv");
+  eo.fuse_se = !f.b("no-fuse-se");
   eo.ln_stats_epilogue = !f.b("no-ln-stats-epilogue");
   eo.tune_in_graph = f.b("tune-in-graph");
   eo.tune_orders = !f.b("no-tune-orders");
@@ -113,7 +114,7 @@ int follower_main(die::Flags& f, sigset_t& sigs) {
 
 const std::vector<std::string> kBoolFlags = {"verbose", "deadline", "no-graphs", "no-device-decode", "dp-follower",
                                              "no-shm", "reuse-port", "dp-no-ingest", "no-pace", "no-pack-text",
-                                             "branch-streams", "coarse-buckets", "no-fuse-pairs", "no-fuse-stem-pool", "fuse-gap-fc", "no-fold-layernorm", "no-tiled-dwconv", "no-poly-dwconv", "no-mfma-gconv", "no-ln-stats-epilogue", "tune-in-graph", "no-tune-orders", "tune-tail", "tune-warm",
+                                             "branch-streams", "coarse-buckets", "no-fuse-pairs", "no-fuse-stem-pool", "fuse-gap-fc", "no-fold-layernorm", "no-tiled-dwconv", "no-poly-dwconv", "no-mfma-gconv", "no-fuse-se", "no-ln-stats-epilogue", "tune-in-graph", "no-tune-orders", "tune-tail", "tune-warm",
                                              "no-efficient-batch", "no-batch-balance",
                                              "dp-force-merge"};
 
@@ -140,7 +141,7 @@ int main(int argc, char** argv) {
               << "  --device auto|hip|cpu (auto)  --device-id N (0)  --precision fp32|bf16 (fp32)\n"
               << "  --pipeline-depth N (3)  --no-graphs  --no-device-decode  --stage-slots N (0 = off, -1 = auto)  --exec-streams N (1)\n"
               << "  --no-pace  --no-pack-text  --branch-streams  --copy-streams N (0 = auto)  --bucket-div N (8)  --coarse-buckets\n"
-              << "  --pace-lead-scale X (1)  --splitk-fused-margin X (0)  --completion-poll-us N (0)  --no-fuse-pairs  --no-fuse-stem-pool  --fuse-gap-fc  --no-fold-layernorm  --no-tiled-dwconv  --no-poly-dwconv  --no-mfma-gconv  --no-ln-stats-epilogue  --tune-in-graph  --no-tune-orders  --tune-tail  --tune-warm  --no-efficient-batch  --efficient-batch-tol X (0)  --tune-cache PATH|auto|''\n"
+              << "  --pace-lead-scale X (1)  --splitk-fused-margin X (0)  --completion-poll-us N (0)  --no-fuse-pairs  --no-fuse-stem-pool  --fuse-gap-fc  --no-fold-layernorm  --no-tiled-dwconv  --no-poly-dwconv  --no-mfma-gconv  --no-fuse-se  --no-ln-stats-epilogue  --tune-in-graph  --no-tune-orders  --tune-tail  --tune-warm  --no-efficient-batch  --efficient-batch-tol X (0)  --tune-cache PATH|auto|''\n"
               << "  --dp-backend rccl|host (rccl)  --dp-force-merge  --fail-batch-every N (fault injection, 0 = off)\n"
               << "  --http-threads N  --parse-threads N (-1 = auto, 0 = parse on the I/O threads)  --parse-spin-us N (0)  --no-batch-balance  --host ADDR (0.0.0.0)\n"
               << "  --devices 0,1,..  data parallel over these GPUs (one process each; --max-batch = whole batch);\n"

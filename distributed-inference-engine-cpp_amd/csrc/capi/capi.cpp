@@ -102,6 +102,7 @@ EngineOptions engine_opts(const Json& j) {
   e.tiled_dwconv = jget<bool>(j, "tiled_dwconv", e.tiled_dwconv);
   e.poly_dwconv = jget<bool>(j, "poly_dwconv", e.poly_dwconv);
   e.mfma_gconv = jget<bool>(j, "mfma_gconv", e.mfma_gconv);
+  e.fuse_se = jget<bool>(j, "fuse_se", e.fuse_se);
   e.ln_stats_epilogue = jget<bool>(j, "ln_stats_epilogue", e.ln_stats_epilogue);
   e.tune_in_graph = jget<bool>(j, "tune_in_graph", e.tune_in_graph);
   e.tune_orders = jget<bool>(j, "tune_orders", e.tune_orders);

@@ -143,6 +143,7 @@ PlanOptions plan_options(int side_branches, int split, int fuse) {
   po.fuse_gap_fc = (fuse & 4) != 0;
   po.fold_layernorm = (fuse & 8) != 0;
   po.ln_stats_epilogue = (fuse & 16) != 0;
+  po.fuse_se = (fuse & 32) == 0;  // the bit turns it OFF: callers that do not know it keep the default
   return po;
 }
 }  // namespace
@@ -594,6 +595,34 @@ int die_kern_grn(const char* geom, uint64_t x, uint64_t gamma, uint64_t beta, ui
   }
 }
 
+// Squeeze-excitation block (kern::se_block): geom's keys are the scalar members of SeArgs.  w2t is the
+// second FC transposed, [Cr][C].  Returns the hipError_t (1 = hipErrorInvalidValue: bad arguments, nothing
+// launched).  die_se_slices: the slice count the launcher picks (slices = 0) before it drops empty slices.
+int die_se_slices(int B, int HW) { return kern::se_slices(B, HW); }
+int die_kern_se(const char* geom, uint64_t x, uint64_t w1, uint64_t b1, uint64_t w2t, uint64_t b2, uint64_t out,
+                uint64_t gate, uint64_t ws, uint64_t counters, uint64_t live, uint64_t stream) {
+  try {
+    kern::SeArgs a;
+    Geom g(geom);
+    g("B", a.B), g("HW", a.HW), g("C", a.C), g("Cr", a.Cr), g("act1", a.act1), g("act2", a.act2), g("alpha", a.alpha);
+    g("beta", a.beta), g("split", a.split), g("ws_bytes", a.ws_bytes), g("counters_n", a.counters_n), g("slices", a.slices);
+    g.done();
+    a.x = P<const uint16_t>(x);
+    a.w1 = P<const float>(w1);
+    a.b1 = P<const float>(b1);
+    a.w2t = P<const float>(w2t);
+    a.b2 = P<const float>(b2);
+    a.out = P<uint16_t>(out);
+    a.gate = P<float>(gate);
+    a.ws = P<float>(ws);
+    a.counters = P<int>(counters);
+    a.live = P<const long long>(live);
+    return static_cast<int>(kern::se_block(a, S(stream)));
+  } catch (...) {
+    return -1;
+  }
+}
+
 int die_kern_softmax(uint64_t x, uint64_t y, uint64_t yf, long long rows, int C, uint64_t stream, int split) {
   return static_cast<int>(kern::softmax_rows(P<const uint16_t>(x), P<uint16_t>(y), P<float>(yf), rows, C, S(stream), split));
 }
@@ -826,6 +855,14 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
         e["gamma"] = o.scale_off != SIZE_MAX;
         e["beta"] = o.shift_off != SIZE_MAX;
       }
+      if (o.kind == PlanOp::SE) {
+        e["C"] = o.C;
+        e["Cr"] = o.Cp;
+        e["rows"] = o.H * o.W;  // pixels of the map
+        e["act1"] = o.act;      // 1 ReLU, 4 SiLU, 5 HardSwish
+        e["act2"] = o.gidx;     // 0 Sigmoid, 1 HardSigmoid
+      }
+      if (o.kind == PlanOp::GCONV) e["act"] = o.act;
       if (o.kind == PlanOp::CONV || o.kind == PlanOp::TOKENS) e["stats_out"] = o.out_stats >= 0;  // writes the partials
       if (o.kind == PlanOp::STEM) {
         e["pool_fused"] = o.is_max != 0;

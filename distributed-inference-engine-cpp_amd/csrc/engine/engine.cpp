@@ -312,6 +312,7 @@ Json engine_options_json(const EngineOptions& o) {
   j["tiled_dwconv"] = o.tiled_dwconv;
   j["poly_dwconv"] = o.poly_dwconv;
   j["mfma_gconv"] = o.mfma_gconv;
+  j["fuse_se"] = o.fuse_se;
   j["ln_stats_epilogue"] = o.ln_stats_epilogue;
   j["tune_in_graph"] = o.tune_in_graph;
   j["tune_orders"] = o.tune_orders;

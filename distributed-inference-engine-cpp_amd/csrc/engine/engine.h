@@ -261,6 +261,9 @@ struct EngineOptions {
   // false: on gconv_kernel with its fp32 weights -- the same bars, not the same bits
   // (profiles/gconv_mfma.md)
   bool mfma_gconv = true;
+  // squeeze-excitation blocks (GlobalAveragePool -> Conv1x1 -> act -> Conv1x1 -> Sigmoid / HardSigmoid ->
+  // Mul) as one SE op (kernels/se.hip, plan_lower_se.cpp); false: the pool, two convs and the elementwise ops
+  bool fuse_se = true;
   bool tune_cold = true;          // autotune with an L2 scrub before each timing (false: back-to-back)
   // after the isolated-launch autotune, time each conv's front runners in place inside eager
   // forwards (input warm from its producer, weights where the previous forward left them) and keep

@@ -55,6 +55,7 @@ HipEngine::HipEngine(const std::string& path, onnx::Model model, const EngineOpt
   po.fuse_gap_fc = opt.fuse_gap_fc;
   po.fold_layernorm = opt.fold_layernorm;
   po.ln_stats_epilogue = opt.ln_stats_epilogue;
+  po.fuse_se = opt.fuse_se;
   plan_ = build_plan(model, max_batch_, po);
   sp_ = plan_.split ? 1 : 0;
   while (n_prep_ops_ < plan_.ops.size() && plan_.ops[n_prep_ops_].kind == PlanOp::INPUT_PREP) {

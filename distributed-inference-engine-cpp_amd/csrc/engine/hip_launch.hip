@@ -371,6 +371,33 @@ hipError_t HipEngine::launch_op(const PlanOp& op, size_t op_index, int B, int s,
       e = kern::grn(g, st);
       break;
     }
+    case PlanOp::SE: {
+      kern::SeArgs g;
+      g.x = cbf(op.in);
+      g.out = bf(op.out);
+      g.w1 = prm(op.w_off);
+      g.b1 = prm(op.bias_off);
+      g.w2t = prm(op.w2_off);
+      g.b2 = prm(op.bias2_off);
+      g.B = B;
+      g.HW = op.H * op.W;
+      g.C = op.C;
+      g.Cr = op.Cp;
+      g.act1 = op.act;
+      g.act2 = op.gidx;
+      g.alpha = op.clip_lo;
+      g.beta = op.clip_hi;
+      g.split = sp_;
+      g.live = live;
+      // a plan buffer of the arena: the gate [B][C], then the slices' partial sums (at most those of B = 1)
+      g.gate = f32(op.out2);
+      g.ws = g.gate + static_cast<size_t>(B) * g.C;
+      g.ws_bytes = kern::se_workspace_bytes(B, kern::se_slices(1, g.HW), g.C);
+      g.counters = counters;  // one per sample, held at 0 between launches like the split-K tile counters
+      g.counters_n = kCounters;
+      e = kern::se_block(g, st);
+      break;
+    }
     case PlanOp::GCONV: {
       kern::GConvArgs g;
       g.x = cbf(op.in);
@@ -486,6 +513,11 @@ Json HipEngine::profile_ops(int B, int iters) {
       o["C"] = op.C;
       o["rows"] = op.H * op.W;
       o["eps"] = static_cast<double>(op.eps);
+    }
+    if (op.kind == PlanOp::SE) {
+      o["C"] = op.C;
+      o["Cr"] = op.Cp;
+      o["rows"] = op.H * op.W;
     }
     total += us[i];
     ops.push_back(o);

@@ -259,6 +259,7 @@ void Planner::lower(int idx) {
   if (op == "Relu") return lower_relu(idx);
   if (op == "Add") return lower_add(idx);
   if (op == "MaxPool" || op == "AveragePool") return lower_pool(idx);
+  if ((op == "GlobalAveragePool" || op == "ReduceMean") && lower_se(idx)) return;  // the head of an SE block
   if (op == "GlobalAveragePool") return lower_gap(idx);
   if (op == "Reshape") return lower_reshape(idx);
   if (op == "Flatten" || op == "Squeeze") return lower_flatten(idx);
@@ -366,8 +367,8 @@ const char* plan_kind_name(PlanOp::Kind kind) {
   static const char* kinds[] = {"input_prep", "conv", "pool", "gap", "affine", "to_nchw_f32", "bf16_to_f32",
                                 "layernorm", "tokens", "gather_rows", "attention", "stem", "gconv", "softmax",
                                 "rows_prep", "copy_cols", "binary", "unary", "conv_pair", "pad", "where", "resize", "bmm", "gap_fc",
-                                "embed_tokens", "pool_tokens", "rope", "groupnorm", "grn"};
-  static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::GRN + 1, "one name per PlanOp kind");
+                                "embed_tokens", "pool_tokens", "rope", "groupnorm", "grn", "se"};
+  static_assert(sizeof(kinds) / sizeof(kinds[0]) == PlanOp::SE + 1, "one name per PlanOp kind");
   return kinds[kind];
 }
 

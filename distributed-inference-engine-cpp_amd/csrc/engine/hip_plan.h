@@ -15,6 +15,8 @@
 //                             Reshape export of GroupNorm, with a trailing ReLU / SiLU
 //  * plan_lower_grn.cpp       ConvNeXt-V2's Global Response Normalization: the ReduceL2(two spatial axes) /
 //                             ReduceMean / Add / Div / Mul / Mul / Add / Add chain, channels-last or -first
+//  * plan_lower_se.cpp        squeeze-excitation blocks (GlobalAveragePool -> Conv1x1 -> act -> Conv1x1 -> Sigmoid /
+//                             HardSigmoid -> Mul), and the trailing SiLU / HardSwish matcher the convs share
 //  * plan_lower_general.cpp   everything else: standalone unary / binary / compare / Where / concat / slice
 // Anything the planner cannot lower is rejected with a clear error (the CPU executor still runs such
 // models).
@@ -90,10 +92,16 @@ struct PlanOp {
                 // (groups = Cp: InstanceNorm): out = act((in - mean) * rstd * gamma + beta), scale_off /
                 // shift_off = gamma / beta [Cp] f32 (SIZE_MAX: none), act 0 none, 1 ReLU, 2 SiLU, eps;
                 // out2 = the launch's workspace (kern::group_norm_workspace_bytes per sample)
-    GRN  // Global Response Normalization of the map in [H * W][C] (dense, no pad channels; an image or an
-         // [N, H, W, C] rows view of one): out = gamma * (in * nx) + beta + in with nx = G / (mean_c G + eps),
-         // G[c] = the L2 norm of channel c over the map; scale_off / shift_off = gamma / beta [C] f32
-         // (SIZE_MAX: none); out2 = the launch's workspace (kern::grn_workspace_bytes per sample)
+    GRN,  // Global Response Normalization of the map in [H * W][C] (dense, no pad channels; an image or an
+          // [N, H, W, C] rows view of one): out = gamma * (in * nx) + beta + in with nx = G / (mean_c G + eps),
+          // G[c] = the L2 norm of channel c over the map; scale_off / shift_off = gamma / beta [C] f32
+          // (SIZE_MAX: none); out2 = the launch's workspace (kern::grn_workspace_bytes per sample)
+    SE  // squeeze-excitation block of the image in [H * W][C] (dense, no pad channels; kern::se_block):
+        // out = in * act2(W2 act1(W1 mean(in) + b1) + b2); w_off / bias_off = W1 [Cp = Cr][C] / b1 f32,
+        // w2_off / bias2_off = W2 transposed [Cr][C] / b2 f32 (bias: SIZE_MAX = none), act = act1 (1 ReLU, 4 SiLU,
+        // 5 HardSwish), gidx = act2 (0 Sigmoid, 1 HardSigmoid(clip_lo = alpha, clip_hi = beta)); out2 = per
+        // sample the f32 gate [C] and the partial sums [C] of kern::se_slices(1, H * W) pixel slices (the most
+        // any batch takes); at batch B the gates of all B samples come first, then the partial sums
   } kind;
   std::string name;
   // buffers (-1 = none).  -2 = the graph input (f32 NCHW), -3 = the graph output (f32).
@@ -219,6 +227,7 @@ struct PlanOptions {
   bool fold_layernorm = true;     // LayerNorms read only by GEMMs become statistics ops (fp32 mode only)
   bool ln_stats_epilogue = true;  // ... and those statistics come from the epilogue of the GEMM
                                   // producing the LayerNorm's input where one does
+  bool fuse_se = true;            // squeeze-excitation chains become SE ops (plan_lower_se.cpp)
 };
 
 // Build the plan for batches up to max_batch.  Throws PlanUnsupported on unsupported graphs, listing EVERY node

@@ -161,20 +161,14 @@ void Planner::emit_groupnorm(const Node& n, const std::string& name, const Val& 
     act = 1;
     done_[r] = true;
     cur = m_.nodes[r].outputs[0];
-  } else if (!graph_outputs_.count(cur)) {
+  } else {
     // SiLU: cur read by exactly Sigmoid(cur) and Mul(cur, that) / Mul(that, cur), the Sigmoid by the Mul alone
-    const std::vector<int> cs = consumers(cur);
-    int sg = -1, mu = -1;
-    for (int c : cs) {
-      if (done_[c]) continue;
-      if (m_.nodes[c].op_type == "Sigmoid") sg = c;
-      else if (m_.nodes[c].op_type == "Mul") mu = c;
-    }
-    if (cs.size() == 2 && sg >= 0 && mu >= 0 && next_op(m_.nodes[sg].outputs[0], "Mul") == mu &&
-        m_.nodes[mu].inputs.size() == 2 && other_input(m_.nodes[mu], cur) == m_.nodes[sg].outputs[0]) {
+    std::vector<int> used;
+    std::string out;
+    if (trailing_act(cur, used, out) == 4) {
       act = 2;
-      done_[sg] = done_[mu] = true;
-      cur = m_.nodes[mu].outputs[0];
+      for (int u : used) done_[u] = true;
+      cur = out;
     }
   }
   PlanOp p;

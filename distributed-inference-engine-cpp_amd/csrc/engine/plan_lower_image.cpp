@@ -155,7 +155,13 @@ void Planner::lower_conv(int idx) {
   float clip_lo = 0.f, clip_hi = 0.f;
   std::string res_name;
   c1 = sole_consumer(cur);
-  if (c1 >= 0 && m_.nodes[c1].op_type == "Relu") {
+  std::vector<int> act_nodes;
+  std::string act_out;
+  if (const int act = trailing_act(cur, act_nodes, act_out)) {
+    relu = act;  // SiLU (4) / HardSwish (5) epilogue
+    for (int u : act_nodes) done_[u] = true;
+    cur = act_out;
+  } else if (c1 >= 0 && m_.nodes[c1].op_type == "Relu") {
     relu = 1;
     done_[c1] = true;
     cur = m_.nodes[c1].outputs[0];
@@ -232,7 +238,7 @@ void Planner::lower_conv(int idx) {
   // ResNet stem (7x7/2, pad 3, 4 stored input channels, 64 outputs, plain epilogue): LDS-patch kernel
   const bool stem = KH == 7 && KW == 7 && s == 2 && d == 1 && pads[0] == 3 && pads[1] == 3 && pads[2] == 3 &&
                     pads[3] == 3 && Cstore == 4 && Cout == 64 && res_buf < 0 && bn2 < 0 && need_out1 &&
-                    relu != 3 && !graph_outputs_.count(cur);
+                    relu <= 1 && !graph_outputs_.count(cur);  // the stem kernels know ReLU only
   if (deferred_prep && !stem) {
     in_buf = ensure_nhwc_input(x, n.in(0));
     p.in = in_buf;
@@ -383,7 +389,15 @@ void Planner::lower_gconv(int idx) {
   p.kind = PlanOp::GCONV;
   p.name = n.name;
   p.in = x.buf;
-  p.act = take_act(cur, p.clip_lo, p.clip_hi);
+  std::vector<int> act_nodes;
+  std::string act_out;
+  if (const int act = trailing_act(cur, act_nodes, act_out)) {  // SiLU (4) / HardSwish (5): every grouped kernel takes them
+    p.act = act;
+    for (int u : act_nodes) done_[u] = true;
+    cur = act_out;
+  } else {
+    p.act = take_act(cur, p.clip_lo, p.clip_hi);
+  }
   // fp32 weights [Cout][KH][KW][cpg] with the BN scale folded
   std::vector<float> w(static_cast<size_t>(Cout) * KH * KW * cpg);
   for (int co = 0; co < Cout; ++co)

@@ -310,6 +310,11 @@ class Planner {
   bool grn_anchor(const Node& n) const;
   void lower_grn(int idx);
 
+  // ---- plan_lower_se.cpp ----
+  // SiLU (4) / HardSwish (5) behind `cur`, 0 if none: the nodes in `used`, the activated value in `out`
+  int trailing_act(const std::string& cur, std::vector<int>& used, std::string& out) const;
+  bool lower_se(int idx);
+
   // ---- plan_lower_general.cpp ----
   bool scalar_init(const std::string& name, float& v) const;
   void lower_compare(int idx);

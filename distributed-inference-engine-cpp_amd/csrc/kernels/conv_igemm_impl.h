@@ -20,8 +20,16 @@ constexpr int BK = 64;
 
 __device__ __forceinline__ int swz(int row, int chunk) { return row * BK + ((chunk ^ ((row >> 1) & 7)) << 3); }
 
-// Epilogue activation: 1 = ReLU, 2 = exact (erf) GELU, 3 = Clip(lo, hi).
+// Epilogue activation: 1 = ReLU, 2 = exact (erf) GELU, 3 = Clip(lo, hi), 4 = SiLU (groupnorm.hip's form),
+// 5 = HardSwish.
 __device__ __forceinline__ float act_fn(float v, int act, float lo = 0.f, float hi = 0.f) {
+  if (act >= 4) {
+    // The empty volatile statement keeps this a real (uniform) branch: without it the compiler computes the
+    // few instructions of both forms for every element and selects, which cost the ReLU epilogues of the
+    // ResNet50 forward 1 - 2 us per conv (profiles/se_mbconv.md).
+    asm volatile("");
+    return act == 4 ? v * __builtin_amdgcn_rcpf(1.f + __expf(-v)) : v * fminf(fmaxf(fmaf(v, 1.f / 6.f, 0.5f), 0.f), 1.f);
+  }
   if (act == 3) return fminf(fmaxf(v, lo), hi);
   return act == 1 ? fmaxf(v, 0.f) : gelu_erf(v);
 }

@@ -37,6 +37,8 @@ namespace {
 __device__ __forceinline__ float dw_act(float v, int act, float lo, float hi) {
   if (act == 1) return fmaxf(v, 0.f);
   if (act == 3) return fminf(fmaxf(v, lo), hi);
+  if (act == 4) return v * __builtin_amdgcn_rcpf(1.f + __expf(-v));             // SiLU
+  if (act == 5) return v * fminf(fmaxf(fmaf(v, 1.f / 6.f, 0.5f), 0.f), 1.f);  // HardSwish
   return v;
 }
 

@@ -304,6 +304,50 @@ struct GrnArgs {
 size_t grn_workspace_bytes(int B, int HW, int C);
 hipError_t grn(const GrnArgs& a, hipStream_t s);
 
+// Squeeze-excitation block of an NHWC map x [B][HW][C] (se.hip), per sample, in two launches:
+//   pool[c] = mean over the HW pixels of x[p][c]
+//   h[r]    = act1(sum_c w1[r][c] * pool[c] + b1[r])            r < Cr
+//   g[c]    = act2(sum_r w2t[r][c] * h[r] + b2[c])              the gate, f32 [B][C]
+//   y       = x * g[c]
+// act1: 1 ReLU, 4 SiLU, 5 HardSwish (the conv epilogue codes); act2: 0 Sigmoid, 1 HardSigmoid =
+// clamp(alpha * v + beta, 0, 1).  w2t is the second FC's [C][Cr] weight transposed to [Cr][C].  All
+// arithmetic between the stored x and the gate is fp32; the gate never takes a bf16 / split rounding.
+// The pixels of a sample are cut into P slices (se_slices, or `slices` when > 0), one block each; with
+// P > 1 the slices' [C] partial sums go through `ws` (>= se_workspace_bytes(B, P, C) bytes) and the last
+// block of a sample to arrive (one counter per sample in `counters`, which must hold 0 and is left at
+// 0) adds them in slice order and runs the FCs: no atomics on data, no block waits for another, the
+// same bits whatever the arrival order, B's place in the batch or *live (P itself follows B).
+// out may be x (in place).  Scope: 8 <= C <= 4096, C % 8 == 0 (no stored pad channels), 1 <= Cr <= 1024,
+// HW >= 1.  Outside it, x / out / ws not 16-byte aligned, an unknown act, a missing gate, or P > 1 with a
+// missing / too small workspace or fewer than B counters: hipErrorInvalidValue, nothing launched.
+struct SeArgs {
+  const uint16_t* x = nullptr;
+  uint16_t* out = nullptr;
+  const float* w1 = nullptr;   // [Cr][C]
+  const float* b1 = nullptr;   // [Cr], nullable (0)
+  const float* w2t = nullptr;  // [Cr][C]
+  const float* b2 = nullptr;   // [C], nullable (0)
+  int B = 1, HW = 1, C = 8, Cr = 1;
+  int act1 = 1, act2 = 0;
+  float alpha = 1.f / 6.f, beta = 0.5f;  // HardSigmoid
+  int split = 0;
+  const long long* live = nullptr;
+  float* gate = nullptr;  // [B][C] f32
+  float* ws = nullptr;
+  size_t ws_bytes = 0;
+  int* counters = nullptr;
+  int counters_n = 0;
+  int slices = 0;  // 0: se_slices(B, HW); tests and tools/se_bench.py force it
+};
+constexpr int kSeMaxSlices = 64;
+// Pixel slices per sample: enough blocks to cover the 256 CUs, at least 16 pixels per slice.
+inline int se_slices(int B, int HW) {
+  const int want = (256 + B - 1) / (B < 1 ? 1 : B), cap = HW / 16 < kSeMaxSlices ? HW / 16 : kSeMaxSlices;
+  return want < cap ? want : cap < 1 ? 1 : cap;
+}
+inline size_t se_workspace_bytes(int B, int P, int C) { return P > 1 ? static_cast<size_t>(B) * P * C * sizeof(float) : 0; }
+hipError_t se_block(const SeArgs& a, hipStream_t s);
+
 // Softmax over the last axis of [rows][C] (one wave per row, fp32 math); writes bf16/split `y`
 // (row pitch ld) and/or f32 `y_f32` (dense [rows][C]).  ld = stored row pitch of x and y (0 = C).
 hipError_t softmax_rows(const uint16_t* x, uint16_t* y, float* y_f32, long long rows, int C, hipStream_t s,

@@ -772,6 +772,10 @@ def _sig_kernels():
     L.die_kern_grn.argtypes = [C.c_char_p] + [u64] * 7
     L.die_grn_workspace_bytes.restype = C.c_longlong
     L.die_grn_workspace_bytes.argtypes = [i] * 3
+    L.die_kern_se.restype = i  # (geometry, x, w1, b1, w2t, b2, out, gate, ws, counters, live, stream)
+    L.die_kern_se.argtypes = [C.c_char_p] + [u64] * 11
+    L.die_se_slices.restype = i
+    L.die_se_slices.argtypes = [i] * 2
     L.die_kern_softmax.restype = i
     L.die_kern_softmax.argtypes = [u64, u64, u64, C.c_longlong, i, u64, i]
     L.die_kern_layernorm.restype = i
@@ -821,8 +825,9 @@ def geometry(members: Dict[str, Any]) -> bytes:
 def plan_summary(model_path: str, max_batch: int = 32, side_branches: bool = False,
                  precision: str = "bf16", fuse_pairs: bool = True, fuse_stem_pool: bool = True,
                  fuse_gap_fc: bool = False, fold_layernorm: bool = True,
-                 ln_stats_epilogue: bool = True) -> Dict[str, Any]:
+                 ln_stats_epilogue: bool = True, fuse_se: bool = True) -> Dict[str, Any]:
     """precision "fp32" plans the split (hi, lo) kernels of the HIP engine's default mode.
+    fuse_se: squeeze-excitation chains as one se op (EngineOptions::fuse_se);
     fuse_pairs: expand + next reduce 1x1 convs as one conv_pair op (EngineOptions::fuse_pairs);
     fuse_stem_pool: stem conv + max pool as one stem op (EngineOptions::fuse_stem_pool);
     fuse_gap_fc: global pool + FC head as one gap_fc op (EngineOptions::fuse_gap_fc);
@@ -832,7 +837,7 @@ def plan_summary(model_path: str, max_batch: int = 32, side_branches: bool = Fal
     err = _err_box()
     p = L.die_plan_summary(model_path.encode(), max_batch, int(side_branches), int(precision == "fp32"),
                            int(fuse_pairs) | 2 * int(fuse_stem_pool) | 4 * int(fuse_gap_fc) | 8 * int(fold_layernorm)
-                           | 16 * int(ln_stats_epilogue), C.byref(err))
+                           | 16 * int(ln_stats_epilogue) | 32 * int(not fuse_se), C.byref(err))
     if not p:
         _raise_if(err, "plan")
     return json.loads(_take_str(p))
@@ -841,7 +846,7 @@ def plan_summary(model_path: str, max_batch: int = 32, side_branches: bool = Fal
 def plan_dump(model_path: str, max_batch: int = 32, side_branches: bool = False,
               precision: str = "bf16", fuse_pairs: bool = True, fuse_stem_pool: bool = True,
               fuse_gap_fc: bool = False, fold_layernorm: bool = True,
-              ln_stats_epilogue: bool = True) -> str:
+              ln_stats_epilogue: bool = True, fuse_se: bool = True) -> str:
     """The whole plan as text, for identity checks (tools/plan_dump.py): an "op" line per op with
     every member, a "buf" line per buffer, a "plan" line with the scalars and a hash of the parameter
     blob.  The arguments of plan_summary."""
@@ -852,7 +857,7 @@ def plan_dump(model_path: str, max_batch: int = 32, side_branches: bool = False,
     err = _err_box()
     p = fn(model_path.encode(), max_batch, int(side_branches), int(precision == "fp32"),
            int(fuse_pairs) | 2 * int(fuse_stem_pool) | 4 * int(fuse_gap_fc) | 8 * int(fold_layernorm)
-           | 16 * int(ln_stats_epilogue), C.byref(err))
+           | 16 * int(ln_stats_epilogue) | 32 * int(not fuse_se), C.byref(err))
     if not p:
         _raise_if(err, "plan")
     return _take_str(p)

@@ -813,7 +813,7 @@ def grouped_conv(x_nhwc, w, bias=None, stride=1, pads=(0, 0, 0, 0), groups=1, cl
     wp = w.float().permute(0, 2, 3, 1).contiguous()
     bp = None if bias is None else bias.float().contiguous()
     out = torch.empty(((2,) if split else ()) + (B, Ho, Wo, Cout), dtype=torch.bfloat16, device=x_nhwc.device)
-    act = 3 if clip is not None else (1 if relu else 0)
+    act = 3 if clip is not None else int(relu)  # relu: a bool, or the epilogue code 4 (SiLU) / 5 (HardSwish)
     lo, hi = clip if clip is not None else (0.0, 0.0)
     geom = dict(B=B, H=H, W=W, Cin=Cin, Ho=Ho, Wo=Wo, Cout=Cout, groups=groups, KH=KH, KW=KW, stride=stride,
                 pad_h=pads[0], pad_w=pads[1], act=act, clip_lo=float(lo), clip_hi=float(hi), split=int(split))
@@ -854,7 +854,7 @@ def depthwise_conv(x_nhwc, w, bias=None, pads=(0, 0, 0, 0), stride=1, dilation=1
         if of is not None:
             of.fill_(fill)
     lv = None if live is None else torch.tensor([int(live)], dtype=torch.int64, device=dev)
-    act = 3 if clip is not None else (1 if relu else 0)
+    act = 3 if clip is not None else int(relu)  # relu: a bool, or the epilogue code 4 (SiLU) / 5 (HardSwish)
     lo, hi = clip if clip is not None else (0.0, 0.0)
     geom = dict(B=B, H=H, W=W, Cin=C, Ho=Ho, Wo=Wo, Cout=Cout, groups=C if groups is None else groups, KH=KH, KW=KW,
                 stride=stride, dil=dilation, pad_h=pads[0], pad_w=pads[1], act=act, clip_lo=float(lo), clip_hi=float(hi),
@@ -927,7 +927,7 @@ def grouped_conv_mfma(x_nhwc, w, bias=None, pads=(0, 0, 0, 0), stride=1, dilatio
         if of is not None:
             of.fill_(fill)
     lv = None if live is None else torch.tensor([int(live)], dtype=torch.int64, device=dev)
-    act = 3 if clip is not None else (1 if relu else 0)
+    act = 3 if clip is not None else int(relu)  # relu: a bool, or the epilogue code 4 (SiLU) / 5 (HardSwish)
     lo, hi = clip if clip is not None else (0.0, 0.0)
     geom = dict(B=B, H=H, W=W, Cin=C, Ho=Ho, Wo=Wo, Cout=Cout, groups=groups, KH=KH, KW=KW, stride=stride,
                 dil=dilation, pad_h=pads[0], pad_w=pads[1], act=act, clip_lo=float(lo), clip_hi=float(hi), split=int(split))
@@ -1008,6 +1008,62 @@ def grn(x_nhwc, gamma=None, beta=None, eps=1e-6, split=False, live=None, fill=No
                                        _ptr(lv), _stream())
     _check(rc, "grn")
     return out
+
+
+SE_ACT1 = {"relu": 1, "silu": 4, "hardswish": 5}  # SeArgs::act1: the conv epilogue codes
+SE_ACT2 = {"sigmoid": 0, "hardsigmoid": 1}
+_se_counters = {}  # device -> the per-sample tickets of se_block: zeroed once, left at 0 by every launch
+
+
+def se_block(x_nhwc, w1, b1, w2, b2, act1="relu", act2="sigmoid", alpha=1.0 / 6.0, beta=0.5, split=False, live=None,
+             slices=0, out=None, fill=None):
+    """Squeeze-excitation block (csrc/kernels/se.hip) of x [B,H,W,C] (any float dtype; a contiguous bf16 tensor
+    of the stored shape, [B,H,W,C] or split [2,B,H,W,C], is read where it is):
+    gate = act2(w2 @ act1(w1 @ mean_hw(x) + b1) + b2), y = x * gate.  w1 [Cr,C], w2 [C,Cr] (transposed here for
+    the kernel), b1 [Cr] / b2 [C] or None; act1 "relu" | "silu" | "hardswish" (or the code 1 / 4 / 5), act2
+    "sigmoid" | "hardsigmoid" (0 / 1) with HardSigmoid = clamp(alpha * v + beta, 0, 1).  live: number of leading
+    samples to compute (a device-side count; the others keep `fill`, in y and in the gate).  slices: pixel
+    slices per sample (0: the launcher's choice).  out: a caller's buffer of the stored shape, which may be the
+    stored planes of x themselves (in place); an error leaves it as it was.
+    Returns (y stored planes: bf16 [B,H,W,C] or [2,B,H,W,C] hi / lo when split, gate f32 [B,C]).  Bad arguments
+    raise NativeError with hipError 1 and launch nothing."""
+    import torch
+
+    B, H, W, C = x_nhwc.shape[-4:]
+    dev = x_nhwc.device
+    stored = ((2,) if split else ()) + (B, H, W, C)
+    if x_nhwc.dtype == torch.bfloat16 and tuple(x_nhwc.shape) == stored and x_nhwc.is_contiguous():
+        xin = x_nhwc
+    else:
+        assert x_nhwc.dim() == 4
+        xin = _in(x_nhwc, split) if split else x_nhwc.to(torch.bfloat16).contiguous()
+    Cr = int(w1.shape[0])
+    assert tuple(w1.shape) == (Cr, C) and tuple(w2.shape) == (C, Cr)
+    w1p = w1.float().contiguous()
+    w2t = w2.float().t().contiguous()
+    b1p = None if b1 is None else b1.float().contiguous()
+    b2p = None if b2 is None else b2.float().contiguous()
+    if out is None:
+        out = torch.empty(stored, dtype=torch.bfloat16, device=dev)
+    assert tuple(out.shape) == stored and out.dtype == torch.bfloat16 and out.is_contiguous()
+    gate = torch.empty((B, C), dtype=torch.float32, device=dev)
+    if fill is not None:
+        out.fill_(fill)
+        gate.fill_(fill)
+    L = native.kernels()
+    P = max(1, min(int(slices) if slices else int(L.die_se_slices(B, H * W)), 64))
+    nbytes = B * P * C * 4
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=dev)
+    if dev not in _se_counters or _se_counters[dev].numel() < B:
+        _se_counters[dev] = torch.zeros(max(B, 1024), dtype=torch.int32, device=dev)
+    cnt = _se_counters[dev]
+    lv = None if live is None else torch.tensor([int(live)], dtype=torch.int64, device=dev)
+    geom = dict(B=B, HW=H * W, C=C, Cr=Cr, act1=SE_ACT1.get(act1, act1), act2=SE_ACT2.get(act2, act2), alpha=float(alpha),
+                beta=float(beta), split=int(split), ws_bytes=nbytes, counters_n=int(cnt.numel()), slices=int(slices))
+    rc = L.die_kern_se(json.dumps(geom).encode(), _ptr(xin), _ptr(w1p), _ptr(b1p), _ptr(w2t), _ptr(b2p), _ptr(out),
+                       _ptr(gate), _ptr(ws), _ptr(cnt), _ptr(lv), _stream())
+    _check(rc, "se_block")
+    return out, gate
 
 
 def softmax_rows(x, split=False):
