@@ -40,8 +40,8 @@ $(BUILD)/hip/%.o: $(SRC)/kernels/%.hip $(wildcard $(SRC)/kernels/*.h)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-# gconv_mfma.hip and dwconv_poly.hip are built without the packed fp32 VALU instructions
-$(BUILD)/hip/gconv_mfma.o $(BUILD)/hip/dwconv_poly.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# gconv_mfma.hip, gconv_wide.hip and dwconv_poly.hip are built without the packed fp32 VALU instructions
+$(BUILD)/hip/gconv_mfma.o $(BUILD)/hip/gconv_wide.o $(BUILD)/hip/dwconv_poly.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(LIBDIR)/libdie.so: $(HOST_OBJS) $(HIP_OBJS)
 	@mkdir -p $(LIBDIR)

@@ -546,6 +546,27 @@ int die_kern_gconv_mfma(const char* geom, uint64_t x, uint64_t w_packed, long lo
   }
 }
 
+// Grouped 3x3 conv on the wide-group MFMA kernel (kern::grouped_conv_wide), the arguments of
+// die_kern_gconv_mfma: w_packed = the bf16 weights of kern::gconv_wide_pack.  Returns the hipError_t
+// (1 = hipErrorInvalidValue: outside the scope, nothing launched).
+int die_kern_gconv_wide(const char* geom, uint64_t x, uint64_t w_packed, long long wplane, uint64_t bias, uint64_t res,
+                        uint64_t out, uint64_t out_f32, uint64_t live, uint64_t stream) {
+  try {
+    kern::GConvArgs a = gconv_geometry(geom);
+    a.x = P<const uint16_t>(x);
+    a.wp = P<const uint16_t>(w_packed);
+    a.wplane = wplane;
+    a.bias = P<const float>(bias);
+    a.res = P<const uint16_t>(res);
+    a.out = P<uint16_t>(out);
+    a.out_f32 = P<float>(out_f32);
+    a.live = P<const long long>(live);
+    return static_cast<int>(kern::grouped_conv_wide(a, S(stream)));
+  } catch (...) {
+    return -1;
+  }
+}
+
 // GroupNorm / InstanceNorm (kern::group_norm): geom's keys are the scalar members of GroupNormArgs.
 // Returns the hipError_t (1 = hipErrorInvalidValue: bad arguments, nothing launched).
 long long die_groupnorm_workspace_bytes(int B, int HW, int C, int G) {
@@ -827,6 +848,7 @@ char* die_plan_summary(const char* model_path, int max_batch, int side_branches,
         e["tiled"] = o.tiled != 0;  // in the scope of the tiled depthwise kernel (kernels/dwconv.hip)
         e["poly"] = o.poly != 0;    // marked for the polyphase depthwise kernel (kernels/dwconv_poly.hip)
         e["mfma"] = o.mfma != 0;    // in the scope of the MFMA grouped 3x3 kernel (kernels/gconv_mfma.hip)
+        e["wide"] = o.wide != 0;    // marked for the wide-group MFMA kernel (kernels/gconv_wide.hip)
         e["KH"] = o.kh;
         e["stride"] = o.sh;
         e["groups"] = o.groups;

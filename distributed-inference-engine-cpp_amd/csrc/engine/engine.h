@@ -257,9 +257,10 @@ struct EngineOptions {
   // depthwise 3x3 (stride 1 / 2) and stride-2 5x5 convs (PlanOp::poly) on the polyphase tiled kernel
   // (kernels/dwconv_poly.hip); false: on gconv_kernel -- the same bits (profiles/dwconv_poly.md)
   bool poly_dwconv = true;
-  // grouped 3x3 convs of width 4 / 8 / 16 / 32 (PlanOp::mfma) on the MFMA kernel (kernels/gconv_mfma.hip);
-  // false: on gconv_kernel with its fp32 weights -- the same bars, not the same bits
-  // (profiles/gconv_mfma.md)
+  // grouped convs on the matrix cores: grouped 3x3 convs of width 4 / 8 / 16 / 32 (PlanOp::mfma) on the MFMA
+  // kernel (kernels/gconv_mfma.hip) and those of width 24 / 40 / 48 / 56 / 64 (PlanOp::wide) on the wide-group
+  // one (kernels/gconv_wide.hip); false: on gconv_kernel with its fp32 weights -- the same bars, not the same
+  // bits (profiles/gconv_mfma.md, profiles/gconv_wide.md)
   bool mfma_gconv = true;
   // squeeze-excitation blocks (GlobalAveragePool -> Conv1x1 -> act -> Conv1x1 -> Sigmoid / HardSigmoid ->
   // Mul) as one SE op (kernels/se.hip, plan_lower_se.cpp); false: the pool, two convs and the elementwise ops

@@ -434,6 +434,10 @@ hipError_t HipEngine::launch_op(const PlanOp& op, size_t op_index, int B, int s,
         g.wp = reinterpret_cast<const uint16_t*>(prm(op.mfma_w_off));
         g.wplane = op.mfma_wplane;
         e = kern::grouped_conv_mfma(g, st);
+      } else if (op.wide && opt_.mfma_gconv) {
+        g.wp = reinterpret_cast<const uint16_t*>(prm(op.wide_w_off));
+        g.wplane = op.wide_wplane;
+        e = kern::grouped_conv_wide(g, st);
       } else {
         e = kern::grouped_conv(g, st);
       }

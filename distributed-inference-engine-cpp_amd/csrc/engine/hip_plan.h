@@ -137,6 +137,13 @@ struct PlanOp {
   int mfma = 0;
   size_t mfma_w_off = SIZE_MAX;
   long long mfma_wplane = 0;
+  // GCONV in the scope of the wide-group MFMA kernel (kern::grouped_conv_wide: the same geometry, group
+  // width 24 / 40 / 48 / 56 / 64, any group count) whose (width, stride) class is turned on
+  // (kern::gconv_wide_class_on): wide = 1, wide_w_off / wide_wplane = the weights of kern::gconv_wide_pack;
+  // never together with mfma.  The same option picks the kernel (EngineOptions::mfma_gconv)
+  int wide = 0;
+  size_t wide_w_off = SIZE_MAX;
+  long long wide_wplane = 0;
   float clip_lo = 0.f, clip_hi = 0.f;  // act == 3 (Clip) of AFFINE / GCONV
   long long rows_per_sample = 0;  // AFFINE / LAYERNORM: rows of C per sample
   // transformer ops: sequence length, heads, head dim, column offsets / pitches of in/in2/in3

@@ -451,6 +451,12 @@ void Planner::lower_gconv(int idx) {
       p.mfma = 1;
       p.mfma_w_off = push_bf16(kern::gconv_mfma_pack(wt.f.data(), scale.data(), Cout, cpg, opt_.split, p.mfma_wplane));
     }
+    // ... and of the wide-group kernel (widths 24 - 64 but 32): the (width, stride) classes that measured
+    // faster than gconv_kernel (profiles/gconv_wide.md)
+    if (kern::grouped_conv_wide_supported(ga) && kern::gconv_wide_class_on(cpg, s)) {
+      p.wide = 1;
+      p.wide_w_off = push_bf16(kern::gconv_wide_pack(wt.f.data(), scale.data(), Cout, cpg, opt_.split, p.wide_wplane));
+    }
   }
   p.groups = G;
   p.C = x.C;

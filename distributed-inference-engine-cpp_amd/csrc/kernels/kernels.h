@@ -178,8 +178,8 @@ struct GConvArgs {
   float clip_lo = 0.f, clip_hi = 0.f;
   int split = 0;
   const long long* live = nullptr;
-  // grouped_conv_mfma only: the packed bf16 weights (gconv_mfma_pack) and, in split mode, the distance
-  // in elements from the hi plane to the lo plane
+  // grouped_conv_mfma / grouped_conv_wide only: the packed bf16 weights (gconv_mfma_pack /
+  // gconv_wide_pack) and, in split mode, the distance in elements from the hi plane to the lo plane
   const uint16_t* wp = nullptr;
   long long wplane = 0;
 };
@@ -227,6 +227,55 @@ inline std::vector<uint16_t> gconv_mfma_pack(const float* wt, const float* scale
         }
       }
   }
+  wplane = split ? static_cast<long long>(n) : 0;
+  return q;
+}
+// Grouped 3x3 convolution on the matrix cores for the wide group widths (gconv_wide.hip): the same
+// arguments and epilogue as grouped_conv_mfma, the weights of gconv_wide_pack in wp / wplane.  Scope:
+// 3x3, dilation 1, stride 1 or 2, pads >= 0, Cin == Cout == C = groups * w with w in {24, 40, 48, 56,
+// 64} (w % 8 == 0, 24 <= w <= 64, w != 32) and any groups >= 1; anything else returns
+// hipErrorInvalidValue and launches nothing.
+inline bool grouped_conv_wide_supported(const GConvArgs& a) {  // host only: the planner's mark rule too
+  if (a.KH != 3 || a.KW != 3 || a.dil != 1 || (a.stride != 1 && a.stride != 2) || a.pad_h < 0 || a.pad_w < 0) return false;
+  if (a.groups < 1 || a.Cin != a.Cout || a.Cout % a.groups) return false;
+  const int w = a.Cout / a.groups;
+  return w % 8 == 0 && w >= 24 && w <= 64 && w != 32;
+}
+hipError_t grouped_conv_wide(const GConvArgs& a, hipStream_t s);
+// The planner's mark rule (PlanOp::wide): the (group width, stride) classes of the scope in which the
+// kernel beat gconv_kernel by more than the spread on every model shape (profiles/gconv_wide.md).  A
+// class that is off stays reachable through grouped_conv_wide itself.
+inline bool gconv_wide_class_on(int w, int stride) { return true; }
+// Weights of grouped_conv_wide: fp32 [C][w][3][3] (ONNX order; scale as in gconv_mfma_pack) ->
+// [groups][NB * 16][Kp] bf16, NB = ceil(w / 16) bundles per group (rows >= w of the last one zero),
+// k = tap * w + ci with no padding between taps, Kp = 9 w rounded up to a multiple of 32 (zeros).
+// split: the hi plane, then the lo plane `wplane` elements after it (0 when not split).
+// ops/kernels.py pack_gconv_wide_weight mirrors it.
+inline std::vector<uint16_t> gconv_wide_pack(const float* wt, const float* scale, int C, int w, bool split,
+                                             long long& wplane) {
+  const int rows = (w + 15) / 16 * 16, Kp = (9 * w + 31) / 32 * 32;
+  const size_t n = static_cast<size_t>(C / w) * rows * Kp;
+  std::vector<uint16_t> q(n * (split ? 2 : 1), 0);
+  auto bf = [](float f) {  // round to nearest even, like the device's f2bf
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return static_cast<uint16_t>((u >> 16) | 0x40);
+    return static_cast<uint16_t>((u + 0x7fffu + ((u >> 16) & 1)) >> 16);
+  };
+  for (int co = 0; co < C; ++co)
+    for (int ci = 0; ci < w; ++ci)
+      for (int tap = 0; tap < 9; ++tap) {
+        const float v = wt[(static_cast<size_t>(co) * w + ci) * 9 + tap] * (scale ? scale[co] : 1.f);
+        const size_t k = (static_cast<size_t>(co / w) * rows + co % w) * Kp + tap * w + ci;
+        const uint16_t hi = bf(v);
+        q[k] = hi;
+        if (split) {
+          const uint32_t hu = static_cast<uint32_t>(hi) << 16;
+          float hf;
+          std::memcpy(&hf, &hu, 4);
+          q[n + k] = bf(v - hf);
+        }
+      }
   wplane = split ? static_cast<long long>(n) : 0;
   return q;
 }

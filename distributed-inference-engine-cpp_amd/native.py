@@ -764,6 +764,8 @@ def _sig_kernels():
     L.die_kern_dwconv_poly.argtypes = [C.c_char_p] + [u64] * 8
     L.die_kern_gconv_mfma.restype = i  # (geometry, x, w_packed, wplane, bias, res, out, out_f32, live, stream)
     L.die_kern_gconv_mfma.argtypes = [C.c_char_p, u64, u64, C.c_longlong] + [u64] * 6
+    L.die_kern_gconv_wide.restype = i  # the same arguments
+    L.die_kern_gconv_wide.argtypes = [C.c_char_p, u64, u64, C.c_longlong] + [u64] * 6
     L.die_kern_groupnorm.restype = i  # (geometry, x, gamma, beta, out, ws, live, stream)
     L.die_kern_groupnorm.argtypes = [C.c_char_p] + [u64] * 7
     L.die_groupnorm_workspace_bytes.restype = C.c_longlong

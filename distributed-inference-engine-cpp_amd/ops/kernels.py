@@ -899,7 +899,7 @@ def pack_gconv_mfma_weight(w, split=False):
 
 
 def grouped_conv_mfma(x_nhwc, w, bias=None, pads=(0, 0, 0, 0), stride=1, dilation=1, clip=None, relu=False,
-                      residual=None, split=False, want_f32=False, live=None, fill=None, groups=1):
+                      residual=None, split=False, want_f32=False, live=None, fill=None, groups=1, _wide=False):
     """Grouped conv with the whole epilogue on the MFMA kernel (csrc/kernels/gconv_mfma.hip).  x [B,H,W,C] (bf16,
     or any float dtype with split), w [Cout, Cin/groups, k, k] float, pads [top, left, bottom, right], residual
     [B,Ho,Wo,Cout] added after the activation, live: number of leading samples to compute (a device-side count; the
@@ -913,9 +913,10 @@ def grouped_conv_mfma(x_nhwc, w, bias=None, pads=(0, 0, 0, 0), stride=1, dilatio
     Wo = (W + pads[1] + pads[3] - dilation * (KW - 1) - 1) // stride + 1
     dev = x_nhwc.device
     xin = _in(x_nhwc, split) if split else x_nhwc.to(torch.bfloat16).contiguous()
-    in_scope = (KH == 3 and KW == 3 and cpg in (4, 8, 16, 32) and Cout == C and cpg * groups == C)
+    widths, pack = ((24, 40, 48, 56, 64), pack_gconv_wide_weight) if _wide else ((4, 8, 16, 32), pack_gconv_mfma_weight)
+    in_scope = (KH == 3 and KW == 3 and cpg in widths and Cout == C and cpg * groups == C)
     # outside the scope nothing is read: the launcher refuses the geometry before it looks at the weights
-    wp, wplane = pack_gconv_mfma_weight(w, split) if in_scope else (w.float().contiguous(), 1)
+    wp, wplane = pack(w, split) if in_scope else (w.float().contiguous(), 1)
     bp = None if bias is None else bias.float().contiguous()
     rp = None
     if residual is not None:
@@ -931,10 +932,34 @@ def grouped_conv_mfma(x_nhwc, w, bias=None, pads=(0, 0, 0, 0), stride=1, dilatio
     lo, hi = clip if clip is not None else (0.0, 0.0)
     geom = dict(B=B, H=H, W=W, Cin=C, Ho=Ho, Wo=Wo, Cout=Cout, groups=groups, KH=KH, KW=KW, stride=stride,
                 dil=dilation, pad_h=pads[0], pad_w=pads[1], act=act, clip_lo=float(lo), clip_hi=float(hi), split=int(split))
-    rc = native.kernels().die_kern_gconv_mfma(json.dumps(geom).encode(), _ptr(xin), _ptr(wp), int(wplane), _ptr(bp),
-                                              _ptr(rp), _ptr(out), _ptr(of), _ptr(lv), _stream())
-    _check(rc, "grouped_conv_mfma")
+    entry = native.kernels().die_kern_gconv_wide if _wide else native.kernels().die_kern_gconv_mfma
+    rc = entry(json.dumps(geom).encode(), _ptr(xin), _ptr(wp), int(wplane), _ptr(bp), _ptr(rp), _ptr(out), _ptr(of),
+               _ptr(lv), _stream())
+    _check(rc, "grouped_conv_wide" if _wide else "grouped_conv_mfma")
     return out, of
+
+
+def pack_gconv_wide_weight(w, split=False):
+    """[C, cw, 3, 3] float (cw = C / groups in {24, 40, 48, 56, 64}) -> the weights of the wide-group MFMA kernel,
+    the torch mirror of kern::gconv_wide_pack (csrc/kernels/kernels.h): [groups][NB * 16][Kp] bf16, NB = ceil(cw / 16)
+    (rows >= cw of a group zero), k = tap * cw + ci, Kp = 9 cw rounded up to a multiple of 32.  split: the hi plane,
+    then the lo plane.  Returns (packed, plane distance in elements: 0 when not split)."""
+    import torch
+
+    C, cw = int(w.shape[0]), int(w.shape[1])
+    G, rows, Kp = C // cw, (cw + 15) // 16 * 16, (9 * cw + 31) // 32 * 32
+    full = torch.zeros((G, rows, Kp), dtype=torch.float32, device=w.device)
+    full[:, :cw, :9 * cw] = w.float().reshape(G, cw, cw, 9).permute(0, 1, 3, 2).reshape(G, cw, 9 * cw)
+    return (split_planes(full), G * rows * Kp) if split else (full.to(torch.bfloat16), 0)
+
+
+def grouped_conv_wide(x_nhwc, w, bias=None, pads=(0, 0, 0, 0), stride=1, dilation=1, clip=None, relu=False,
+                      residual=None, split=False, want_f32=False, live=None, fill=None, groups=1):
+    """grouped_conv_mfma on the wide-group MFMA kernel (csrc/kernels/gconv_wide.hip: group widths 24 / 40 / 48 / 56
+    / 64, any group count): the same arguments (relu: a bool, or the epilogue code 4 = SiLU / 5 = HardSwish) and the
+    same return.  A geometry outside the kernel's scope raises NativeError with hipError 1 and launches nothing."""
+    return grouped_conv_mfma(x_nhwc, w, bias, pads, stride, dilation, clip, relu, residual, split, want_f32, live, fill,
+                             groups, _wide=True)
 
 
 GN_ACTS = {None: 0, "none": 0, "relu": 1, "silu": 2}
